@@ -12,15 +12,19 @@ common.py:255; SURVEY.md 8d counts it in the step).  The point cloud is resident
 timed region starts; frames are sharded over ranks (rank r renders steps r, r+N, ... of an N*K-step
 path; --video-frames: of ONE video, strong scaling).  Synthetic seeded RGBD input (no datasets / checkpoints are reachable offline).
 
-Timing: W untimed warm-up frames, then passes of EXACTLY K frames, each bracketed by barrier +
-synchronize on both sides (max over ranks), repeated until >= 0.5 s of timed wall; `value` is K * N /
-the MEDIAN pass.  `device_only` is the same loop with the frames left in HBM (no PCIe), reported beside
-it.  The cloud broadcast (multi-GPU) is scene set-up, timed separately as `cloud_broadcast_ms`.
+Timing: at least W untimed warm-up frames (whole passes of the K frames: every shape the timed pass
+uses is warm; and at least WARMUP_MIN_S of them), then ONE pass of EXACTLY K timed frames, bracketed by barrier +
+synchronize on both sides (max over ranks); `value` is K * N / that pass, `ms_per_step` the pass / K.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (the scatter =
-render_pointcloud: SURVEY.md 8d's 28 N + 20 HW bytes over the HIP-event time of its launches, measured
-live) and `cpu_baseline` (the CPU oracle timed on this host, rank 0 at N=1 only -- the oracle is
-used here as the baseline, never as the product path).
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run does nothing else: set-up, warm-up,
+the K timed frames, the outputs (--dump-outputs DIR: the last timed frame as float32 .npy), the line.
+--full adds, after the timed pass, what is measured beside the headline: `device_only` (the same loop
+with the frames left in HBM, no PCIe: passes of K frames until >= 0.5 s, median), `frames_check`
+(delivered frames against those left in HBM), `roofline` (the scatter = render_pointcloud: SURVEY.md
+8d's 28 N + 20 HW bytes over the HIP-event time of its launches, measured live), `cpu_baseline` (the
+CPU oracle timed on this host, rank 0 at N=1 only -- the oracle is used here as the baseline, never as
+the product path) and, multi-GPU, `cloud_broadcast_ms` (the cloud broadcast is scene set-up, timed on
+its own).
 """
 import argparse
 import json
@@ -480,7 +484,13 @@ def pipeline_bench(args, device):
             ts.append(time.perf_counter() - t0)
         return float(np.median(ts)), ts
 
-    call_s, call_ts = timed(lambda: pipe(image, zoom), K, Wm)
+    last = {}
+
+    def call():
+        last['frames'] = pipe(image, zoom)
+    call_s, call_ts = timed(call, K, Wm)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'frames': np.stack(last['frames'])})
     # where the call's time goes: its three parts on their own (each synchronised: their sum exceeds the call by the overlap it loses)
     oc = pipe.objectCommon
     est_s, _ = timed(lambda: pipe.estimate(image), 5, 1)
@@ -577,6 +587,27 @@ def pipeline_bench(args, device):
     print(json.dumps(line), flush=True)
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much in all
+# seconds of warm-up passes at least, whatever W: the clocks need load before the one timed pass (--steps 20 --warmup 5, k frames/s:
+# 14.0-14.1 after the 20 frames of one warm-up pass alone, 14.7 after 0.2 s of them -- what the median of 200 passes read)
+WARMUP_MIN_S = 0.2
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every {name: array} as DIR/<name>.npy in float32.  An array larger than its share of DUMP_MAX_BYTES keeps a
+    fixed sample of its rows (leading axis, seeded: the same rows in every run), and the rows kept go beside it as DIR/<name>_rows.npy."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1) - (1 << 20)          # (1 MB of each share left for a row list)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(directory, name + '_rows.npy'), rows.astype(np.float64))
+        np.save(os.path.join(directory, name + '.npy'), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` (N > 1, no WORLD_SIZE): start N ranks of this script under torch.distributed.run, one process per
     GPU, rendezvous on 127.0.0.1 -- the same command line the driver uses when it starts the ranks itself.  Rank 0's JSON line
@@ -595,11 +626,11 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=1024, help='timed frames per rank (a 128-frame video repeated is the same work; long enough for the queue ramp to vanish)')
-    ap.add_argument('--warmup', type=int, default=128, help='untimed frames first (the clocks need a few ms of load: 8 frames read 6 %% slower than 256)')
+    ap.add_argument('--steps', type=int, default=1024, help='timed frames per rank, one pass (a 128-frame video repeated is the same work; long enough for the queue ramp to vanish)')
+    ap.add_argument('--warmup', type=int, default=128, help='untimed frames first, at least this many, as whole passes of the --steps frames for at least 0.2 s (the clocks need load: 8 frames read 6 %% slower than 256)')
     ap.add_argument('--size', type=int, default=1024)
     ap.add_argument('--dolly', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no cpu_baseline')
     ap.add_argument('--no-crop', action='store_true')
     ap.add_argument('--device-only', action='store_true',
                     help='leave the finished frames in HBM: `value` is then NOT the SURVEY 8d step (dev comparison; config.delivery says so)')
@@ -616,6 +647,12 @@ def main():
                          'a pass renders the whole video once, --steps is ignored')
     ap.add_argument('--cloud', choices=['inpaint', 'raw'], default='inpaint',
                     help='inpaint: grow the cloud with the (seeded) Inpaint network as the pipeline does; raw: image pixels only')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed pass, also measure what stands beside the headline: device_only, frames_check, roofline, cpu_baseline '
+                         '(unless --no-cpu-baseline), cloud_broadcast_ms (multi-GPU)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the frame the timed pass computed last (rank 0) as DIR/frame_last.npy, float32 [H, W, 3] '
+                         '(--pipeline: the last timed video\'s frames as DIR/frames.npy, rows sampled past 64 MB)')
     args = ap.parse_args()
 
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')     # before the first HIP call: RCCL needs dmabuf IPC on this stack
@@ -718,7 +755,7 @@ def main():
     # landing buffers of the timed runs are allocated (and every page touched) here, not in the loop
     delivery = 'hbm' if args.device_only else 'pinned_host'
     host_out = None if args.device_only else torch.zeros(max(n_mine, 1), size, size, 3, dtype=torch.uint8, pin_memory=True)
-    dev_out = torch.zeros(max(n_mine, 1), size, size, 3, dtype=torch.uint8, device=device)
+    dev_out = torch.zeros(max(n_mine, 1), size, size, 3, dtype=torch.uint8, device=device) if args.device_only or args.full else None
 
     def run_host():
         return common.render_frames(cams, oc, crop, host_out=host_out, overlap=not args.no_overlap, batch=args.batch)
@@ -726,11 +763,19 @@ def main():
     def run_device():
         return common.render_frames(cams, oc, crop, keep_on_device=True, host_out=dev_out)
 
-    # warm-up (untimed): W frames on both routes (clocks, staging buffers, streams, first-touch of the pinned pages)
-    nw = max(min(args.warmup, n_mine), 1)
-    common.render_frames(cams[:nw], oc, crop, keep_on_device=True, host_out=dev_out[:nw])
-    if host_out is not None:
-        common.render_frames(cams[:nw], oc, crop, host_out=host_out[:nw], overlap=not args.no_overlap, batch=args.batch)
+    run = run_device if args.device_only else run_host
+    # warm-up (untimed): at least W frames, as whole passes of the timed K frames -- the transfer groups, staging buffers and the
+    # delivery lanes' probe of a video depend on its length, so only the pass itself warms every shape the timed pass uses (streams,
+    # first-touch of the pinned pages besides) -- and at least WARMUP_MIN_S of them, for the clocks.  --full: W frames on the HBM
+    # route too, which it times beside.
+    warm_passes, t0 = 0, time.perf_counter()
+    while warm_passes == 0 or warm_passes * n_mine < args.warmup or time.perf_counter() - t0 < WARMUP_MIN_S:
+        run()
+        torch.cuda.synchronize()
+        warm_passes += 1
+    if args.full and host_out is not None:
+        nw = max(min(args.warmup, n_mine), 1)
+        common.render_frames(cams[:nw], oc, crop, keep_on_device=True, host_out=dev_out[:nw])
 
     def sync():
         torch.cuda.synchronize()
@@ -740,9 +785,9 @@ def main():
 
     # the one exchange step of a video: the finished cloud goes from rank 0 to every rank (RCCL broadcast).  It is
     # scene set-up like build_scene above, not part of a frame step, so it is timed on its own and reported as
-    # `cloud_broadcast_ms` beside the frame rate (a video pays it once, whatever its length)
+    # `cloud_broadcast_ms` beside the frame rate (a video pays it once, whatever its length) -- with --full
     broadcast_ms = None
-    if world_size > 1:
+    if world_size > 1 and args.full:
         sync()
         t0 = time.perf_counter()
         sharding.broadcast_cloud(oc, device)
@@ -773,18 +818,20 @@ def main():
             times.append(timed_pass(run))
         return times
 
-    # THE timed region: passes of K frames, cloud resident in HBM, finished uint8 frames delivered to pinned host memory
-    # (--device-only: left in HBM); the HBM-resident rate is measured the same way and reported beside it
-    times = timed(run_device if args.device_only else run_host)
-    elapsed = float(np.median(times))
-    own_elapsed = float(np.median(own_times))
-    times_dev = times if args.device_only else timed(run_device)
-    elapsed_dev = float(np.median(times_dev))
+    # THE timed region: one pass of K frames, cloud resident in HBM, finished uint8 frames delivered to pinned host memory
+    # (--device-only: left in HBM)
+    times = [timed_pass(run)]
+    elapsed = times[0]
+    own_elapsed = own_times[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'frame_last': (dev_out if args.device_only else host_out)[n_mine - 1].cpu().numpy()})
+    # --full: the HBM-resident rate, passes of K frames until >= 0.5 s, reported beside it
+    times_dev = times if args.device_only else (timed(run_device) if args.full else None)
 
     # the delivered frames against the frames left in HBM (two runs of the same cameras; the accumulation order may differ in the
     # last bit): the first and the last frame of the pass, every value
     frames_check = None
-    if host_out is not None:
+    if host_out is not None and args.full:
         worst = 0
         for k in (0, n_mine // 2, n_mine - 1):
             d = (host_out[k].to(torch.int16) - dev_out[k].cpu().to(torch.int16)).abs()
@@ -819,88 +866,6 @@ def main():
         state = common._prepared_cloud(_native.kernels(), oc)
         video_flags, group_used, fused_used = _native.kernels().video_launch_shape(state, cams, args.batch, to_host=not args.device_only)
         route = 'fused' if fused_used else 'bucket'
-        group_frames = group_used if group_used > 1 else GROUP_FRAMES
-        fill_flags = 32 | (512 if video_flags & 1 else 0)           # KBE_STAGE_FILL_BY_COUNT, + KBE_STAGE_FILL_DIST where the loop fills with the tables
-        # the camera paths the scatter's launch is priced on: this run's own, the product's 75 steps, the driver's 20 (consecutive
-        # cameras in groups of `group_frames`: time_kernels)
-        paths = {}
-        if not args.dolly:
-            for n_steps in dict.fromkeys((total_steps, PRODUCT_STEPS, DRIVER_STEPS)):
-                paths[str(n_steps)] = common.frame_cameras(dict(settings, dblSteps=np.linspace(0.0, 1.0, max(n_steps, 2)).tolist()[:n_steps]), oc)
-        kt = time_kernels(oc, cams, route, fill_rect=None if crop is None else common.crop_window(size, size, crop[0], crop[1]), group_frames=group_frames,
-                          fill_flags=fill_flags, paths=paths, fill_group=group_used if (video_flags & 1) else 1)
-        HW = size * size
-        # roofline = the scatter (render_pointcloud, common.py:428-686: z-buffer clear + z-splat + degrid + accumulate +
-        # normalise), SURVEY.md 8d: algorithmic bytes 28 N + 20 HW (every input once, every output once, no scratch) per frame
-        # over the HIP-event time of the launches that implement it, back to back alone on a stream -- for the route and the
-        # number of frames per launch the timed region took (fused: k_place + k_frame; bucket: k_project + k_tiles, the tile
-        # launch clearing the other frame's z-buffer), with the one-frame launches and the other route beside it.
-        scatter_bytes = 28 * n_points + 20 * HW
-        # (the fused route's tile launch also makes the next group's placements -- k_frame_ahead / k_frame_group_ahead -- unless KBE_AHEAD=0)
-        ahead = os.environ.get('KBE_AHEAD') != '0' and 'fused:scatter_group_ahead' in kt and 'fused:scatter_ahead' in kt
-        route_launches = {'fused': ['k_frame_ahead'] if ahead else ['k_place', 'k_frame'], 'bucket': ['k_project', 'k_tiles'], 'fused:two_launches': ['k_place', 'k_frame']}
-        # the committed PMC passes are of the default workload and of configs[4] (2048^2 from 16.8 M points) only
-        default_workload = size == 1024 and args.cloud == 'inpaint' and not args.dolly and args.upsample == 1
-        config4_workload = size == 2048 and args.upsample == 2 and not args.dolly
-        per_kernel, traffic_src = measured_traffic() if default_workload else (measured_traffic('_config4') if config4_workload else ({}, None))
-        insts, insts_src = measured_instructions() if default_workload else ({}, None)
-
-        def roof(r, frames):
-            if r == 'bucket':
-                frames = min(frames, BUCKET_GROUP_MAX)
-            names = route_launches[r]
-            one_launch = names == ['k_frame_ahead']
-            r = r.split(':')[0]
-            t = kt[r + (':scatter_group' if frames > 1 else ':scatter') + ('_ahead' if one_launch else '')]
-            tr = sum(per_kernel[k] for k in names) if all(k in per_kernel for k in names) else None
-            tr_launch = None if tr is None else frames * tr
-            # a group launch measured as such (the frames of a group share their candidate lists: the one-frame launch's figures
-            # times the frames overstate it)
-            group_name = 'k_frame_group_ahead' if one_launch else ('k_frame_group' if names == ['k_place', 'k_frame'] else None)
-            g_traffic = per_kernel.get('by_frames_per_launch', {}).get(group_name, {}).get(str(frames)) if frames > 1 and one_launch else None
-            g_insts = insts.get('by_frames_per_launch', {}).get(group_name, {}).get(str(frames)) if frames > 1 and one_launch else None
-            if g_traffic:
-                tr_launch = g_traffic['hbm_bytes']
-            out = {'route': r, 'kernel': ' + '.join(n.replace('k_frame', 'k_frame_group').replace('k_tiles', 'k_tiles_group').replace('k_project', 'k_project_group')
-                                                    if frames > 1 else n for n in names), 'frames_per_launch': frames,
-                   'us': round(t * 1e6, 2), 'us_per_frame': round(t * 1e6 / frames, 2), 'algorithmic_bytes': frames * scatter_bytes,
-                   'achieved': frames * scatter_bytes / t / 1e9, 'frac': frames * scatter_bytes / t / 1e9 / HBM_PEAK_GBS,
-                   'traffic': tr_launch}
-            if g_traffic:
-                out['traffic_note'] = 'PMC on launches of %d frames' % frames
-            if g_insts or all(k in insts for k in names):
-                # the other roofline these launches live under: wave-level VALU instructions per frame over the chip's issue rate
-                n_valu = g_insts['valu'] / frames if g_insts else sum(insts[k]['valu'] for k in names)
-                out['valu_issue'] = {'insts_per_frame': n_valu, 'us_at_peak': round(n_valu / VALU_ISSUE_PER_US, 2),
-                                     'frac': n_valu / VALU_ISSUE_PER_US / (t * 1e6 / frames)}
-            return out
-        frames_per_launch = group_used
-        main = roof(route, frames_per_launch)
-        single = roof(route, 1)
-        grouped = roof(route, group_frames)
-        other = roof('bucket' if route == 'fused' else 'fused', group_frames)
-        two_launches = roof('fused:two_launches', group_frames) if route == 'fused' and ahead else None
-        # the group launch on consecutive cameras of real paths (the frames of a group share candidate lists built for the box
-        # between the group's first and last camera: identical cameras are the best case).  The line's `roofline` is priced on the
-        # PRODUCT's path (75 steps, /root/reference/kbe.py:104) when the timed region launches groups; this run's own path, the
-        # driver's 20 steps and the identical-camera figure are kept beside it.
-        by_path = {}
-        for label in paths:
-            t = kt.get('fused:scatter_group_ahead:consecutive:' + label)
-            if t:
-                fpl = min(group_frames, len(paths[label]))      # (a path shorter than a launch: one group of all its frames)
-                by_path[label] = {'steps': int(label), 'groups': len(consecutive_groups(paths[label], group_frames)), 'frames_per_launch': fpl,
-                                  'us': round(t * 1e6, 2), 'us_per_frame': round(t * 1e6 / fpl, 2),
-                                  'achieved': fpl * scatter_bytes / t / 1e9, 'frac': fpl * scatter_bytes / t / 1e9 / HBM_PEAK_GBS,
-                                  'rounds_us': [round(x * 1e6, 2) for x in kt['fused:scatter_group_ahead:consecutive:' + label + ':rounds']]}
-        cameras_note, identical = 'identical (one camera, %d copies per launch)' % frames_per_launch, None
-        if route == 'fused' and ahead and frames_per_launch == group_frames and str(PRODUCT_STEPS) in by_path:
-            c = by_path[str(PRODUCT_STEPS)]
-            identical = {k: main[k] for k in ('us', 'us_per_frame', 'achieved', 'frac')}
-            main = dict(main, us=c['us'], us_per_frame=c['us_per_frame'], achieved=c['achieved'], frac=c['frac'])
-            if 'valu_issue' in main:
-                main['valu_issue'] = dict(main['valu_issue'], frac=main['valu_issue']['us_at_peak'] / c['us_per_frame'])
-            cameras_note = 'consecutive: groups of %d consecutive cameras of a %d-step path (the last group: the path\'s last %d), group k placing group k + 1 ahead' % (group_frames, PRODUCT_STEPS, group_frames)
         cloud = ('raw' if args.dolly else args.cloud) if args.upsample == 1 else '%dx-upsampled' % args.upsample ** 2
         line = {
             'metric': 'novel_view_frames_per_sec_%dx%d' % (size, size), 'value': total_steps / elapsed,
@@ -911,54 +876,138 @@ def main():
             'config': {'workload': '%dx%d %s path, %d pts (%s cloud), frame=shift+scatter+fill+u8%s' % (
                            size, size, 'dolly' if args.dolly else 'KBE', n_points, cloud, '' if crop is None else '+crop/resize'),
                        'delivery': delivery, 'scatter_route': route, 'frames_per_rank': n_mine, 'lanes': lanes if args.device_only else host_lanes,
-                       'device_only_lanes': lanes, 'passes': len(times),
+                       'device_only_lanes': lanes, 'warmup_frames': warm_passes * n_mine, 'passes': len(times),
                        'pass_ms': {'median': round(elapsed * 1e3, 3), 'min': round(min(times) * 1e3, 3), 'max': round(max(times) * 1e3, 3)},
                        'sharding': 'frames %s over ranks (sharding.shard_indices); one cloud broadcast (set-up, cloud_broadcast_ms)' % os.environ.get('KBE_SHARD_SHAPE', sharding.SHARD_SHAPE),
                        'handoff': ('sdma' if _native.handoff_by_sdma() else 'blit (hipMemcpyAsync)') if not args.device_only else None,
                        'collectives': backend if world_size > 1 else None, 'ranks_seen': ranks_seen},
-            'device_only': {'value': total_steps / elapsed_dev, 'unit': 'frames/s', 'ms_per_step': elapsed_dev / (total_steps if strong else args.steps) * 1e3,
-                            'passes': len(times_dev), 'note': 'same K frames left in HBM (no PCIe hand-off)'},
-            'roofline': {'bound': 'hbm', 'kernel': main['kernel'] + ' (the scatter = render_pointcloud, %s route)' % route,
-                         'achieved': main['achieved'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': main['frac'],
-                         'traffic': main['traffic'], 'traffic_source': traffic_src, 'algorithmic_bytes': main['algorithmic_bytes'],
-                         'frames_per_launch': frames_per_launch, 'us': main['us'], 'us_per_frame': main['us_per_frame'],
-                         'cameras': cameras_note, 'by_path': by_path, 'identical_cameras': identical,
-                         'formula': '28 N + 20 HW per frame (SURVEY.md 8d)',
-                         'valu_issue': main.get('valu_issue'), 'valu_issue_source': insts_src,
-                         'one_frame_per_launch': single, 'grouped': grouped, 'other_route': other, 'placement_launch_in_front': two_launches,
-                         'note': 'launches timed alone on one stream, back to back (HIP events, 40 repetitions), with the number of frames per '
-                                 'launch the timed region uses; fused route: ONE launch per group -- the tile launch of a group also makes the placements '
-                                 'of the next group, so a launch holds all of the scatter\'s work for its frames (`cameras` says which cameras a group holds); '
-                                 'the matching rocprofv3 --stats summary is profiles/*scatter_group*_kernel_stats.csv '
-                                 '(in the timed region the kernels of several lanes overlap and per-kernel durations stretch)',
-                         'kernel_us': {k: ([round(x * 1e6, 2) for x in v] if isinstance(v, list) else round(v * 1e6, 2)) for k, v in kt.items()}},
         }
-        # the hole fill (fill_disocclusion, common.py:833-937) under the same roofline: SURVEY.md 8d's 36 HW bytes per frame (the render
-        # and the depth plane in, the render out) over the HIP-event time of its launches (k_hole_dist + k_fill_tables + k_fill_holes
-        # where the loop fills with the tables, else k_fill_holes), mean over eight cameras along the path.  Where it takes longer per
-        # frame than the scatter -- a dolly zoom without inpainting -- it is the line's `roofline`, the scatter's figures beside it.
-        fill_t = kt['fill_along_path']
-        fill_obj = {'bound': 'hbm', 'kernel': ('k_hole_dist + k_fill_tables + k_fill_holes' if video_flags & 1 else 'k_fill_holes') + ' (fill_disocclusion)',
-                    'achieved': 36 * HW / max(fill_t, 1e-9) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': 36 * HW / max(fill_t, 1e-9) / 1e9 / HBM_PEAK_GBS,
-                    'traffic': None, 'algorithmic_bytes': 36 * HW, 'formula': '36 HW per frame (SURVEY.md 8d)', 'us_per_frame': round(fill_t * 1e6, 2),
-                    'us_worst_of_eight_cameras': round(kt['fill_along_path_max'] * 1e6, 2),
-                    'note': 'a frame on its own on one stream (HIP events, 40 repetitions), with and without its fill, eight cameras along the path; '
-                            'the walk is bound by instruction issue and the number of holes, not by these bytes'}
-        if 'fill_group_along_path' in kt:
-            # the fill's launches as the video loop makes them: `frames_per_launch` frames each (the single-frame figure stays beside it)
-            g_t, g_n = kt['fill_group_along_path'], kt['fill_group_frames']
-            fill_obj['one_frame_per_launch'] = {k: fill_obj[k] for k in ('achieved', 'frac', 'us_per_frame', 'us_worst_of_eight_cameras')}
-            fill_obj.update({'frames_per_launch': g_n, 'us': round(g_t * 1e6, 2), 'us_per_frame': round(g_t * 1e6 / g_n, 2), 'algorithmic_bytes': g_n * 36 * HW,
-                             'achieved': g_n * 36 * HW / max(g_t, 1e-9) / 1e9, 'frac': g_n * 36 * HW / max(g_t, 1e-9) / 1e9 / HBM_PEAK_GBS,
-                             'us_worst_of_eight_cameras': round(kt['fill_group_along_path_max'] * 1e6 / g_n, 2),
-                             'note': 'the fill launches of %d consecutive frames (what the video loop launches: KBE_VIDEO_FILL_GROUP) alone on one stream (HIP events, 40 repetitions), with and '
-                                     'without their fill, at eight places along the path; `one_frame_per_launch`: a frame on its own; the walk is bound by instruction issue, '
-                                     'dependent look-ups and the number of holes, not by these bytes' % g_n})
-        if fill_t * 1e6 > single['us_per_frame']:          # (like with like: both a frame on its own)
-            fill_obj['scatter'] = line['roofline']
-            line['roofline'] = fill_obj
-        else:
-            line['roofline']['fill'] = fill_obj
+        if args.full:
+            group_frames = group_used if group_used > 1 else GROUP_FRAMES
+            fill_flags = 32 | (512 if video_flags & 1 else 0)           # KBE_STAGE_FILL_BY_COUNT, + KBE_STAGE_FILL_DIST where the loop fills with the tables
+            # the camera paths the scatter's launch is priced on: this run's own, the product's 75 steps, the driver's 20 (consecutive
+            # cameras in groups of `group_frames`: time_kernels)
+            paths = {}
+            if not args.dolly:
+                for n_steps in dict.fromkeys((total_steps, PRODUCT_STEPS, DRIVER_STEPS)):
+                    paths[str(n_steps)] = common.frame_cameras(dict(settings, dblSteps=np.linspace(0.0, 1.0, max(n_steps, 2)).tolist()[:n_steps]), oc)
+            kt = time_kernels(oc, cams, route, fill_rect=None if crop is None else common.crop_window(size, size, crop[0], crop[1]), group_frames=group_frames,
+                              fill_flags=fill_flags, paths=paths, fill_group=group_used if (video_flags & 1) else 1)
+            HW = size * size
+            # roofline = the scatter (render_pointcloud, common.py:428-686: z-buffer clear + z-splat + degrid + accumulate +
+            # normalise), SURVEY.md 8d: algorithmic bytes 28 N + 20 HW (every input once, every output once, no scratch) per frame
+            # over the HIP-event time of the launches that implement it, back to back alone on a stream -- for the route and the
+            # number of frames per launch the timed region took (fused: k_place + k_frame; bucket: k_project + k_tiles, the tile
+            # launch clearing the other frame's z-buffer), with the one-frame launches and the other route beside it.
+            scatter_bytes = 28 * n_points + 20 * HW
+            # (the fused route's tile launch also makes the next group's placements -- k_frame_ahead / k_frame_group_ahead -- unless KBE_AHEAD=0)
+            ahead = os.environ.get('KBE_AHEAD') != '0' and 'fused:scatter_group_ahead' in kt and 'fused:scatter_ahead' in kt
+            route_launches = {'fused': ['k_frame_ahead'] if ahead else ['k_place', 'k_frame'], 'bucket': ['k_project', 'k_tiles'], 'fused:two_launches': ['k_place', 'k_frame']}
+            # the committed PMC passes are of the default workload and of configs[4] (2048^2 from 16.8 M points) only
+            default_workload = size == 1024 and args.cloud == 'inpaint' and not args.dolly and args.upsample == 1
+            config4_workload = size == 2048 and args.upsample == 2 and not args.dolly
+            per_kernel, traffic_src = measured_traffic() if default_workload else (measured_traffic('_config4') if config4_workload else ({}, None))
+            insts, insts_src = measured_instructions() if default_workload else ({}, None)
+
+            def roof(r, frames):
+                if r == 'bucket':
+                    frames = min(frames, BUCKET_GROUP_MAX)
+                names = route_launches[r]
+                one_launch = names == ['k_frame_ahead']
+                r = r.split(':')[0]
+                t = kt[r + (':scatter_group' if frames > 1 else ':scatter') + ('_ahead' if one_launch else '')]
+                tr = sum(per_kernel[k] for k in names) if all(k in per_kernel for k in names) else None
+                tr_launch = None if tr is None else frames * tr
+                # a group launch measured as such (the frames of a group share their candidate lists: the one-frame launch's figures
+                # times the frames overstate it)
+                group_name = 'k_frame_group_ahead' if one_launch else ('k_frame_group' if names == ['k_place', 'k_frame'] else None)
+                g_traffic = per_kernel.get('by_frames_per_launch', {}).get(group_name, {}).get(str(frames)) if frames > 1 and one_launch else None
+                g_insts = insts.get('by_frames_per_launch', {}).get(group_name, {}).get(str(frames)) if frames > 1 and one_launch else None
+                if g_traffic:
+                    tr_launch = g_traffic['hbm_bytes']
+                out = {'route': r, 'kernel': ' + '.join(n.replace('k_frame', 'k_frame_group').replace('k_tiles', 'k_tiles_group').replace('k_project', 'k_project_group')
+                                                        if frames > 1 else n for n in names), 'frames_per_launch': frames,
+                       'us': round(t * 1e6, 2), 'us_per_frame': round(t * 1e6 / frames, 2), 'algorithmic_bytes': frames * scatter_bytes,
+                       'achieved': frames * scatter_bytes / t / 1e9, 'frac': frames * scatter_bytes / t / 1e9 / HBM_PEAK_GBS,
+                       'traffic': tr_launch}
+                if g_traffic:
+                    out['traffic_note'] = 'PMC on launches of %d frames' % frames
+                if g_insts or all(k in insts for k in names):
+                    # the other roofline these launches live under: wave-level VALU instructions per frame over the chip's issue rate
+                    n_valu = g_insts['valu'] / frames if g_insts else sum(insts[k]['valu'] for k in names)
+                    out['valu_issue'] = {'insts_per_frame': n_valu, 'us_at_peak': round(n_valu / VALU_ISSUE_PER_US, 2),
+                                         'frac': n_valu / VALU_ISSUE_PER_US / (t * 1e6 / frames)}
+                return out
+            frames_per_launch = group_used
+            main = roof(route, frames_per_launch)
+            single = roof(route, 1)
+            grouped = roof(route, group_frames)
+            other = roof('bucket' if route == 'fused' else 'fused', group_frames)
+            two_launches = roof('fused:two_launches', group_frames) if route == 'fused' and ahead else None
+            # the group launch on consecutive cameras of real paths (the frames of a group share candidate lists built for the box
+            # between the group's first and last camera: identical cameras are the best case).  The line's `roofline` is priced on the
+            # PRODUCT's path (75 steps, the reference's kbe.py:104) when the timed region launches groups; this run's own path, the
+            # driver's 20 steps and the identical-camera figure are kept beside it.
+            by_path = {}
+            for label in paths:
+                t = kt.get('fused:scatter_group_ahead:consecutive:' + label)
+                if t:
+                    fpl = min(group_frames, len(paths[label]))      # (a path shorter than a launch: one group of all its frames)
+                    by_path[label] = {'steps': int(label), 'groups': len(consecutive_groups(paths[label], group_frames)), 'frames_per_launch': fpl,
+                                      'us': round(t * 1e6, 2), 'us_per_frame': round(t * 1e6 / fpl, 2),
+                                      'achieved': fpl * scatter_bytes / t / 1e9, 'frac': fpl * scatter_bytes / t / 1e9 / HBM_PEAK_GBS,
+                                      'rounds_us': [round(x * 1e6, 2) for x in kt['fused:scatter_group_ahead:consecutive:' + label + ':rounds']]}
+            cameras_note, identical = 'identical (one camera, %d copies per launch)' % frames_per_launch, None
+            if route == 'fused' and ahead and frames_per_launch == group_frames and str(PRODUCT_STEPS) in by_path:
+                c = by_path[str(PRODUCT_STEPS)]
+                identical = {k: main[k] for k in ('us', 'us_per_frame', 'achieved', 'frac')}
+                main = dict(main, us=c['us'], us_per_frame=c['us_per_frame'], achieved=c['achieved'], frac=c['frac'])
+                if 'valu_issue' in main:
+                    main['valu_issue'] = dict(main['valu_issue'], frac=main['valu_issue']['us_at_peak'] / c['us_per_frame'])
+                cameras_note = 'consecutive: groups of %d consecutive cameras of a %d-step path (the last group: the path\'s last %d), group k placing group k + 1 ahead' % (group_frames, PRODUCT_STEPS, group_frames)
+            elapsed_dev = float(np.median(times_dev))
+            line['device_only'] = {'value': total_steps / elapsed_dev, 'unit': 'frames/s', 'ms_per_step': elapsed_dev / (total_steps if strong else args.steps) * 1e3,
+                                   'passes': len(times_dev), 'note': 'same K frames left in HBM (no PCIe hand-off)'}
+            line['roofline'] = {'bound': 'hbm', 'kernel': main['kernel'] + ' (the scatter = render_pointcloud, %s route)' % route,
+                                'achieved': main['achieved'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': main['frac'],
+                                'traffic': main['traffic'], 'traffic_source': traffic_src, 'algorithmic_bytes': main['algorithmic_bytes'],
+                                'frames_per_launch': frames_per_launch, 'us': main['us'], 'us_per_frame': main['us_per_frame'],
+                                'cameras': cameras_note, 'by_path': by_path, 'identical_cameras': identical,
+                                'formula': '28 N + 20 HW per frame (SURVEY.md 8d)',
+                                'valu_issue': main.get('valu_issue'), 'valu_issue_source': insts_src,
+                                'one_frame_per_launch': single, 'grouped': grouped, 'other_route': other, 'placement_launch_in_front': two_launches,
+                                'note': 'launches timed alone on one stream, back to back (HIP events, 40 repetitions), with the number of frames per '
+                                        'launch the timed region uses; fused route: ONE launch per group -- the tile launch of a group also makes the placements '
+                                        'of the next group, so a launch holds all of the scatter\'s work for its frames (`cameras` says which cameras a group holds); '
+                                        'the matching rocprofv3 --stats summary is profiles/*scatter_group*_kernel_stats.csv '
+                                        '(in the timed region the kernels of several lanes overlap and per-kernel durations stretch)',
+                                'kernel_us': {k: ([round(x * 1e6, 2) for x in v] if isinstance(v, list) else round(v * 1e6, 2)) for k, v in kt.items()}}
+            # the hole fill (fill_disocclusion, common.py:833-937) under the same roofline: SURVEY.md 8d's 36 HW bytes per frame (the render
+            # and the depth plane in, the render out) over the HIP-event time of its launches (k_hole_dist + k_fill_tables + k_fill_holes
+            # where the loop fills with the tables, else k_fill_holes), mean over eight cameras along the path.  Where it takes longer per
+            # frame than the scatter -- a dolly zoom without inpainting -- it is the line's `roofline`, the scatter's figures beside it.
+            fill_t = kt['fill_along_path']
+            fill_obj = {'bound': 'hbm', 'kernel': ('k_hole_dist + k_fill_tables + k_fill_holes' if video_flags & 1 else 'k_fill_holes') + ' (fill_disocclusion)',
+                        'achieved': 36 * HW / max(fill_t, 1e-9) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': 36 * HW / max(fill_t, 1e-9) / 1e9 / HBM_PEAK_GBS,
+                        'traffic': None, 'algorithmic_bytes': 36 * HW, 'formula': '36 HW per frame (SURVEY.md 8d)', 'us_per_frame': round(fill_t * 1e6, 2),
+                        'us_worst_of_eight_cameras': round(kt['fill_along_path_max'] * 1e6, 2),
+                        'note': 'a frame on its own on one stream (HIP events, 40 repetitions), with and without its fill, eight cameras along the path; '
+                                'the walk is bound by instruction issue and the number of holes, not by these bytes'}
+            if 'fill_group_along_path' in kt:
+                # the fill's launches as the video loop makes them: `frames_per_launch` frames each (the single-frame figure stays beside it)
+                g_t, g_n = kt['fill_group_along_path'], kt['fill_group_frames']
+                fill_obj['one_frame_per_launch'] = {k: fill_obj[k] for k in ('achieved', 'frac', 'us_per_frame', 'us_worst_of_eight_cameras')}
+                fill_obj.update({'frames_per_launch': g_n, 'us': round(g_t * 1e6, 2), 'us_per_frame': round(g_t * 1e6 / g_n, 2), 'algorithmic_bytes': g_n * 36 * HW,
+                                 'achieved': g_n * 36 * HW / max(g_t, 1e-9) / 1e9, 'frac': g_n * 36 * HW / max(g_t, 1e-9) / 1e9 / HBM_PEAK_GBS,
+                                 'us_worst_of_eight_cameras': round(kt['fill_group_along_path_max'] * 1e6 / g_n, 2),
+                                 'note': 'the fill launches of %d consecutive frames (what the video loop launches: KBE_VIDEO_FILL_GROUP) alone on one stream (HIP events, 40 repetitions), with and '
+                                         'without their fill, at eight places along the path; `one_frame_per_launch`: a frame on its own; the walk is bound by instruction issue, '
+                                         'dependent look-ups and the number of holes, not by these bytes' % g_n})
+            if fill_t * 1e6 > single['us_per_frame']:          # (like with like: both a frame on its own)
+                fill_obj['scatter'] = line['roofline']
+                line['roofline'] = fill_obj
+            else:
+                line['roofline']['fill'] = fill_obj
         if frames_check is not None:
             line['frames_check'] = frames_check
             if not frames_check['ok']:          # a rate measured on wrong frames is not a measurement: no headline number, exit status 3
@@ -973,10 +1022,10 @@ def main():
             line['scaling_valid'] = scaling_valid
             if scaling_note:
                 line['scaling_note'] = scaling_note
+            line['config']['rank0_numa_node'] = numa_node
         if broadcast_ms is not None:
             line['cloud_broadcast_ms'] = broadcast_ms
-            line['config']['rank0_numa_node'] = numa_node
-        if world_size == 1 and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(oc, cams, crop)
         print(json.dumps(line), flush=True)
     if world_size > 1:

@@ -8,6 +8,8 @@ import socket
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -138,3 +140,52 @@ def test_pmc_figures_are_quoted_only_from_files_measured_on_these_kernel_sources
     assert bench.measured_traffic() == ({}, None) and 'left out of the line' in capsys.readouterr().err
     (fake / 'profiles' / 'r09_hbm_traffic.json').write_text(json.dumps({'kernels': {'k_frame': {'hbm_bytes': 1.0}}}))        # a file from before the stamp existed
     assert bench.measured_traffic() == ({}, None)
+
+
+def test_dump_outputs_are_float32_within_64_mb_and_sampled_the_same_way_every_run(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): DIR/<name>.npy in float32, at most 64 MB in all; an array past its share keeps a
+    seeded sample of its rows -- the same rows in every run, listed beside it as DIR/<name>_rows.npy."""
+    import numpy as np
+    import bench
+    small = np.arange(2 * 3 * 3, dtype=np.uint8).reshape(2, 3, 3)
+    big = np.random.default_rng(1).integers(0, 256, (4096, 2048, 3), dtype=np.uint8)        # 100 MB as float32
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), {'small': small, 'big': big})
+    files = sorted(f.name for f in (tmp_path / 'a').iterdir())
+    assert files == ['big.npy', 'big_rows.npy', 'small.npy']
+    assert sum((tmp_path / 'a' / f).stat().st_size for f in files) <= 64 * 10 ** 6
+    s, b, rows = (np.load(tmp_path / 'a' / f) for f in ('small.npy', 'big.npy', 'big_rows.npy'))
+    assert s.dtype == np.float32 and np.array_equal(s, small)
+    assert b.dtype == np.float32 and rows.dtype == np.float64 and len(rows) == len(b) > 1000
+    assert np.array_equal(b, big[rows.astype(np.int64)]) and np.all(np.diff(rows) > 0)
+    for f in files:
+        assert (tmp_path / 'a' / f).read_bytes() == (tmp_path / 'b' / f).read_bytes(), f
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_its_steps_and_full_adds_the_rest(tmp_path):
+    """A plain `bench.py --steps K` times ONE pass of exactly K frames and measures nothing beside it; --full adds device_only,
+    frames_check and roofline.  Both write the last timed frame (--dump-outputs) from the same seeded inputs: the same frame up to
+    the order of the fp32 atomics (a count at most, on few pixels)."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'KBE_BENCH_LAUNCH_ONLY'):
+        env.pop(k, None)
+    lines = {}
+    for mode in ('plain', 'full'):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '12', '--warmup', '4', '--size', '256',
+               '--dump-outputs', str(tmp_path / mode)] + (['--full', '--no-cpu-baseline'] if mode == 'full' else [])
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines[mode] = _line(r.stdout)
+    plain, full = lines['plain'], lines['full']
+    for line in (plain, full):
+        assert line['metric'] == 'novel_view_frames_per_sec_256x256' and line['unit'] == 'frames/s' and line['higher_is_better'] is True
+        assert line['dtype'] == 'f32' and line['steps'] == 12 and line['config']['passes'] == 1 and line['config']['frames_per_rank'] == 12
+        assert line['ms_per_step'] > 0 and abs(line['value'] * line['ms_per_step'] / 1e3 - 1) < 1e-9
+    assert not {'device_only', 'frames_check', 'roofline', 'cpu_baseline'} & set(plain)
+    assert {'device_only', 'frames_check', 'roofline'} <= set(full) and full['frames_check']['ok']
+    a, b = np.load(tmp_path / 'plain' / 'frame_last.npy'), np.load(tmp_path / 'full' / 'frame_last.npy')
+    assert a.dtype == np.float32 and a.shape == (256, 256, 3) and a.min() >= 0 and a.max() <= 255 and a.std() > 1
+    d = np.abs(a - b)
+    assert d.max() <= 1 and (d > 0).mean() < 1e-3

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/${1:-prof}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # 1. the default bench command (frames delivered to pinned host memory)
-timeout 900 python $R/bench.py 2> $OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 900 python $R/bench.py --full 2> $OUT/bench.err | tail -1 > $OUT/bench.json
 # 2. the same default command under rocprofv3 --kernel-trace --stats
 rm -rf /tmp/ks
 timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/ks -o b --output-format csv -- python $R/bench.py --no-cpu-baseline 2> $OUT/rocprof.err | tail -1 > $OUT/bench_under_rocprof.json
@@ -22,21 +22,21 @@ python $R/tools/kernel_times.py /tmp/ks1/b_kernel_trace.csv > $OUT/bench_lanes1_
 rm -rf /tmp/ks2
 KBE_FUSED=0 KBE_LANES=1 KBE_HOST_LANES=1 timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/ks2 -o b --output-format csv -- python $R/bench.py --no-cpu-baseline 2>> $OUT/rocprof.err | tail -1 > $OUT/bench_bucket_lanes1_under_rocprof.json
 cp /tmp/ks2/b_kernel_stats.csv $OUT/bench_bucket_lanes1_kernel_stats.csv
-KBE_FUSED=0 timeout 900 python $R/bench.py --no-cpu-baseline 2>> $OUT/bench.err | tail -1 > $OUT/bench_bucket.json
+KBE_FUSED=0 timeout 900 python $R/bench.py --full --no-cpu-baseline 2>> $OUT/bench.err | tail -1 > $OUT/bench_bucket.json
 # 2c'. short videos (the driver's --steps 20 / 75)
-for k in 20 75; do timeout 600 python $R/bench.py --no-cpu-baseline --steps $k --warmup 5 2>> $OUT/bench.err | tail -1 > $OUT/bench_steps$k.json; done
+for k in 20 75; do timeout 600 python $R/bench.py --full --no-cpu-baseline --steps $k --warmup 5 2>> $OUT/bench.err | tail -1 > $OUT/bench_steps$k.json; done
 # 2c''. the other BASELINE configurations, each a bench line with the `roofline` of its dominant kernel: the dolly
 # zoom (configs[3] 4a: its fill), 2048^2 from 16.8 M points (configs[4]), 512^2 (configs[1]'s frame loop)
-timeout 900 python $R/bench.py --no-cpu-baseline --dolly --steps 256 --warmup 32 2>> $OUT/bench.err | tail -1 > $OUT/bench_dolly.json
-timeout 900 python $R/bench.py --no-cpu-baseline --size 2048 --upsample 2 --steps 64 --warmup 8 2>> $OUT/bench.err | tail -1 > $OUT/bench_config4.json
-timeout 900 python $R/bench.py --no-cpu-baseline --size 512 --steps 1024 --warmup 64 2>> $OUT/bench.err | tail -1 > $OUT/bench_512.json
+timeout 900 python $R/bench.py --full --no-cpu-baseline --dolly --steps 256 --warmup 32 2>> $OUT/bench.err | tail -1 > $OUT/bench_dolly.json
+timeout 900 python $R/bench.py --full --no-cpu-baseline --size 2048 --upsample 2 --steps 64 --warmup 8 2>> $OUT/bench.err | tail -1 > $OUT/bench_config4.json
+timeout 900 python $R/bench.py --full --no-cpu-baseline --size 512 --steps 1024 --warmup 64 2>> $OUT/bench.err | tail -1 > $OUT/bench_512.json
 # 2c'''. BASELINE configs[1] as a whole and the 1024^2 partial-convolution forward (bench.py --pipeline), twice: the first process on a fresh
 # box runs MIOpen's find step once (Pipeline(miopen_find='auto')), the second runs in immediate mode on the tuned find-db
 for k in first second; do timeout 900 python $R/bench.py --pipeline --steps 10 --warmup 2 2>> $OUT/bench.err | tail -1 > $OUT/pipeline_${k}_process.json; done
 # 2d. multi-rank code path on this one GPU (gloo; ranks share the device: a functional check, not a measurement)
-KBE_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --gpus 2 --steps 32 --warmup 4 2>> $OUT/bench.err | tail -1 > $OUT/bench_2ranks_gloo_one_gpu.json
+KBE_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --full --gpus 2 --steps 32 --warmup 4 2>> $OUT/bench.err | tail -1 > $OUT/bench_2ranks_gloo_one_gpu.json
 # 2d'. the same code path with configs[4]'s cloud: a 470 MB broadcast (gloo here: a functional check of the size, not an xGMI figure)
-KBE_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --gpus 2 --size 2048 --upsample 2 --steps 8 --warmup 2 2>> $OUT/bench.err | tail -1 > $OUT/bench_config4_2ranks_gloo_one_gpu.json
+KBE_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --full --gpus 2 --size 2048 --upsample 2 --steps 8 --warmup 2 2>> $OUT/bench.err | tail -1 > $OUT/bench_config4_2ranks_gloo_one_gpu.json
 # 3. HBM traffic: one PMC pass per counter (no trace domains alongside)
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pm_$c

@@ -36,7 +36,7 @@ def free_port():
 
 def run_bench(n, extra, env, timeout):
     """One bench.py run on n ranks -> its JSON line (dict), or {'error': ...}."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--no-cpu-baseline'] + extra
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--full', '--no-cpu-baseline'] + extra      # --full: device_only, frames_check, cloud_broadcast_ms
     if n > 1:
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n), '--master-addr', '127.0.0.1',
                '--master-port', str(free_port())] + cmd[1:]
