@@ -42,6 +42,7 @@
 
 #include "kbe_cloud.h"
 #include "kbe_tiles.h"
+#include "kbe_video_plan.h"
 
 using namespace kbe;
 
@@ -763,9 +764,6 @@ __global__ void __launch_bounds__(64) k_signal_wait(volatile int64_t* value, uns
 #ifndef KBE_SDMA_WAIT_SECONDS
 #define KBE_SDMA_WAIT_SECONDS 4.0
 #endif
-#ifndef KBE_SDMA_TWO_ENGINES
-#define KBE_SDMA_TWO_ENGINES 0      // (1: consecutive groups alternate between two engines -- measured slower end to end, see sdma_open)
-#endif
 
 struct SdmaPair {                       // the signals of one copy and where their values live
     hsa_signal_t dep, fin; volatile int64_t* dep_value; volatile int64_t* fin_value;
@@ -797,8 +795,7 @@ static bool sdma_signal(hsa_signal_t& sg, volatile int64_t*& value)
 struct SdmaCall {                               // one kbe_render_video call's use of the engine
     bool ok = false;
     hsa_agent_t gpu = {}, cpu = {};
-    hsa_amd_sdma_engine_id_t engine[2] = { HSA_AMD_SDMA_ENGINE_0, HSA_AMD_SDMA_ENGINE_0 };      // consecutive groups alternate between two engines
-    int sent = 0;
+    hsa_amd_sdma_engine_id_t engine = HSA_AMD_SDMA_ENGINE_0;
     std::vector<SdmaPair> used;
 };
 // which agents own the two buffers, and an engine that copies from the one to the other; false: no SDMA hand-off (the caller
@@ -845,12 +842,10 @@ static bool sdma_open(SdmaCall& c, const void* device_buffer, const void* host_b
     }
     // its lowest engine.  (An engine takes ~9.4 us from the end of one copy to the start of the next even when that one has long been
     // released -- the device-side timeline of a 20-frame video, tools/sdma_timeline.py: five such gaps in 1.35 ms.  With the groups
-    // alternating between TWO engines, KBE_SDMA_TWO_ENGINES, the copies overlap and the last one ends 60 us earlier on the device --
+    // alternating between TWO engines the copies overlap and the last one ends 60 us earlier on the device --
     // and the video is delivered SLOWER: 13.9 instead of 14.6 k frames/s for 20 frames, 16.15 instead of 16.6 k for 75: the host sees
     // the end ~170 us after the device instead of ~30.  One engine it is.)
-    const uint32_t first = pick & (~pick + 1u), rest = pick & ~first, second = rest ? (rest & (~rest + 1u)) : first;
-    c.engine[0] = (hsa_amd_sdma_engine_id_t) first;
-    c.engine[1] = (hsa_amd_sdma_engine_id_t) (KBE_SDMA_TWO_ENGINES ? second : first);
+    c.engine = (hsa_amd_sdma_engine_id_t) (pick & (~pick + 1u));
     c.gpu = dinfo.agentOwner; c.cpu = hinfo.agentOwner;
     // the signals of calls that have run to their end are idle again
     for (size_t g = 0; g < pool.running.size(); ) {
@@ -1301,14 +1296,62 @@ int kbe_render_pointcloud_tiled(const float* points, const float* data, int N, i
     return launched("kbe_render_pointcloud_tiled/reset");
 }
 
+}  // extern "C"
+
 #if defined(KBE_VIDEO_TRACE)
 #include <time.h>
+#define KBE_HOST_TRACE(...) __VA_ARGS__
 static double trace_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
+#else
+#define KBE_HOST_TRACE(...)
 #endif
+#if defined(KBE_VIDEO_GPU_TRACE)
+#define KBE_GPU_TRACE(...) __VA_ARGS__
+#else
+#define KBE_GPU_TRACE(...)
+#endif
+namespace {
 constexpr int KBE_VIDEO_STAGES = KBE_STAGE_PROJECT | KBE_STAGE_TILES | KBE_STAGE_FILL;
-#ifndef KBE_HBM_CONSECUTIVE
-#define KBE_HBM_CONSECUTIVE 1
-#endif
+
+// Dev builds only, the transfer groups of the hand-off: -DKBE_VIDEO_TRACE, where does the host spend the call (tools/handoff_trace.py);
+// -DKBE_VIDEO_GPU_TRACE, when, on the device, a group's frames are ready, its gate opens, its transfer ends (tools/handoff_gpu_trace.py).
+// Without either every hook is empty.
+struct VideoTrace {
+    KBE_HOST_TRACE(double t_call = trace_now(), t_g = 0, t_r = 0, t_t = 0, t_c = 0;)
+    KBE_GPU_TRACE(hipEvent_t ev_start = nullptr; std::vector<hipEvent_t> ev_begin, ev_ready, ev_gate, ev_copied;)
+    void start(int n_groups, hipStream_t cs)
+    {
+        KBE_GPU_TRACE(ev_begin.resize(n_groups); ev_ready.resize(n_groups); ev_gate.resize(n_groups); ev_copied.resize(n_groups);
+                      (void) hipEventCreate(&ev_start); (void) hipEventRecord(ev_start, cs);
+                      for (int g = 0; g < n_groups; g++) { (void) hipEventCreate(&ev_begin[g]); (void) hipEventCreate(&ev_ready[g]); (void) hipEventCreate(&ev_gate[g]); (void) hipEventCreate(&ev_copied[g]); })
+    }
+    void begin(int g, hipStream_t s) { KBE_GPU_TRACE((void) hipEventRecord(ev_begin[g], s);) KBE_HOST_TRACE(t_g = trace_now();) }
+    void ready(int g, hipStream_t s) { KBE_HOST_TRACE(t_r = trace_now();) KBE_GPU_TRACE((void) hipEventRecord(ev_ready[g], s);) }
+    void gate(int g, hipStream_t s) { KBE_GPU_TRACE((void) hipEventRecord(ev_gate[g], s);) KBE_HOST_TRACE(t_t = trace_now();) }
+    void copied(int g, hipStream_t s) { KBE_GPU_TRACE((void) hipEventRecord(ev_copied[g], s);) KBE_HOST_TRACE(t_c = trace_now();) }
+    void sent(int g, const PlanUnit& un)
+    {
+        KBE_HOST_TRACE(fprintf(stderr, "group %3d lane %d frames %3d..%3d: t=%8.1f us  render-enqueue %7.1f  turn %6.1f  hipMemcpyAsync %7.1f  turn %6.1f\n", g, un.lane, un.first,
+                               un.first + un.count - 1, (t_g - t_call) * 1e6, (t_r - t_g) * 1e6, (t_t - t_r) * 1e6, (t_c - t_t) * 1e6, (trace_now() - t_c) * 1e6);)
+    }
+    void finish(const VideoPlan& plan, const hipStream_t* ls, int lanes, size_t fb, int rc)
+    {
+        KBE_GPU_TRACE(
+        for (int l = 0; l < lanes; l++) (void) hipStreamSynchronize(ls[l]);
+        for (int g = 0; g < (int) plan.units.size() && rc == KBE_OK; g++) {
+            const PlanUnit& un = plan.units[g];
+            float b = 0, r = 0, o = 0, c = 0;
+            (void) hipEventElapsedTime(&b, ev_start, ev_begin[g]); (void) hipEventElapsedTime(&r, ev_start, ev_ready[g]);
+            (void) hipEventElapsedTime(&o, ev_start, ev_gate[g]); (void) hipEventElapsedTime(&c, ev_start, ev_copied[g]);
+            fprintf(stderr, "group %3d lane %d frames %3d..%3d: render %8.1f .. %8.1f us, gate open %8.1f, transfer ends %8.1f (%.1f GB/s from the gate)\n", g, un.lane,
+                    un.first, un.first + un.count - 1, b * 1e3, r * 1e3, o * 1e3, c * 1e3, (double) un.count * fb / ((c - o) * 1e6));
+        })
+    }
+};
+}  // namespace
+
+extern "C" {
+
 int kbe_render_video(const float* points, const float* image, const float* depth, int N, int W, int H, double baseline,
                      int n_frames, const double* focals, const float* shifts, int crop_w, int crop_h, void* scratch,
                      uint8_t* stage, int batch, uint8_t* host_out, int raster_w, int raster_n, const void* packed,
@@ -1320,6 +1363,8 @@ int kbe_render_video(const float* points, const float* image, const float* depth
     KBE_REQUIRE((crop_w == 0 && crop_h == 0) || (crop_w > 0 && crop_h > 0 && crop_w <= W && crop_h <= H), "kbe_render_video: bad crop");
     KBE_REQUIRE(lanes >= 1 && lanes <= KBE_MAX_LANES && (lanes == 1 || lane_streams), "kbe_render_video: bad lanes");
     KBE_REQUIRE(near_depth >= 0.0 && near_depth < 1.0e30, "kbe_render_video: near_depth is a depth (0: unknown)");
+    KBE_REQUIRE(scratch && ((uintptr_t) scratch & 15) == 0 && N >= 0 && (packed || (N <= (1 << 30) && (N == 0 || (points && image && depth)))),
+                "kbe_render_video: bad scratch or cloud");
     const hipStream_t cs = (hipStream_t) stream;
     const size_t fb = (size_t) W * H * 3;
     const size_t sb = (scratch_set_bytes(W, H, N) + 255) & ~(size_t) 255;      // == kbe_video_scratch_stride: lane stride
@@ -1334,23 +1379,17 @@ int kbe_render_video(const float* points, const float* image, const float* depth
     const int group = batch <= 0 ? (wide_group > 1 ? wide_group : ((flags >> 1) & 3) + 1) : 1;
     KBE_REQUIRE(group <= (packed ? KBE_FRAME_JOBS : KBE_FILL_JOBS), "kbe_render_video: more frames per launch than the route's launches take");
     KBE_REQUIRE(!packed || N <= KBE_FUSED_MAX_POINTS, "kbe_render_video: the packed cloud's route takes up to 2^28 points (more: the plain cloud's route)");
-    // the fused route always takes the group form (one frame per launch is a group of one): its tile launches also make the
-    // placements of the lane's NEXT group (launch_frames_fused) unless KBE_VIDEO_NO_AHEAD says otherwise
-    const bool pairs = group > 1 || (packed && batch <= 0);
     // Frames are independent, so consecutive frames go to `lanes` HIP streams, each with its own scratch and raw
     // frame: the fixed cost of a kernel boundary on this chip (launch ramp, tail, and the L2 write-back between
     // dependent kernels) is then paid while another frame's kernels run.
     // stage = [KBE_FRAME_JOBS * lanes raw frames][lanes * fin finished frames][ring half 0: batch frames][ring half 1: batch frames].
-    hipStream_t ls[KBE_MAX_LANES], ds[1];
+    hipStream_t ls[KBE_MAX_LANES];
     for (int l = 0; l < lanes; l++) ls[l] = l == 0 ? cs : (hipStream_t) lane_streams[l];
-    ds[0] = copy_stream ? (hipStream_t) copy_stream : cs;        // only the staged ring (batch > 0) uses it
-#if defined(KBE_VIDEO_TRACE)
-    const double t_call = trace_now();
-#endif
+    const hipStream_t dc = copy_stream ? (hipStream_t) copy_stream : cs;        // only the staged ring (batch > 0) uses it
+    VideoTrace trace;
     const int fin = (int) stage_fin_per_lane(batch);                    // finished-frame buffers per lane
-    const int slots = fin * lanes;
     uint8_t* const finished = stage + (size_t) KBE_FRAME_JOBS * lanes * fb;
-    uint8_t* ring[2] = { finished + (size_t) slots * fb, finished + ((size_t) slots + (size_t) (batch > 0 ? batch : 0)) * fb };
+    uint8_t* const ring0 = finished + (size_t) fin * lanes * fb;
     // where do the frames go?  (a pointer the runtime does not know is taken for device memory, as before)
     uint8_t* host_dev = nullptr;                // host_out as the device sees it, when it is pinned host memory
     if (batch <= 0) {
@@ -1364,11 +1403,11 @@ int kbe_render_video(const float* points, const float* image, const float* depth
             (void) hipGetLastError();           // unknown to the runtime: not an error here
         }
     }
-    const bool per_frame = host_dev != nullptr;                         // per-frame hand-off to pinned host memory
+    const VideoDest dest = batch > 0 ? VideoDest::RING : !host_dev ? VideoDest::HBM : batch == 0 ? VideoDest::PER_FRAME : VideoDest::GROUPS;
+    const bool ringed = dest == VideoDest::RING;
     // the hand-off's turn counter sits behind the frame buffers of `stage`, 256-byte aligned
     const size_t ctl_offset = stage_ctl_offset(W, H, lanes, batch);
     KBE_REQUIRE(((uintptr_t) stage & 255) == 0, "kbe_render_video: stage must be 256-byte aligned");
-    const bool ringed = batch > 0;
     int rect[4] = { 0, 0, W - 1, H - 1 };
     if (crop) {
         // the pixels cv2.getRectSubPix reads (common.py:256), padded by one: see kbe_render_frame_stages
@@ -1389,7 +1428,12 @@ int kbe_render_video(const float* points, const float* image, const float* depth
         return e;
     };
     auto destroy = [&]() { for (int k = 0; k < n_ev; k++) (void) hipEventDestroy(pool[k]); };
-    if (per_frame && lanes > 1) {
+    // whoever synchronises `stream` afterwards also sees every frame delivered and every other stream idle
+    auto join = [&]() {
+        for (int l = 1; l < lanes && ok; l++) { hipEvent_t e = make(); if (e) { (void) hipEventRecord(e, ls[l]); (void) hipStreamWaitEvent(cs, e, 0); } }
+        if (ringed && dc != cs && ok) { hipEvent_t e = make(); if (e) { (void) hipEventRecord(e, dc); (void) hipStreamWaitEvent(cs, e, 0); } }
+    };
+    if (host_dev && lanes > 1) {
         // the turn counter of the hand-off starts at 0 for every call (on `stream`, before the other lanes start)
         const hipError_t e = hipMemsetAsync(stage + ctl_offset, 0, sizeof(DeliverCtl), cs);
         if (e != hipSuccess) return fail(KBE_E_LAUNCH, "kbe_render_video: hipMemsetAsync", e);
@@ -1402,342 +1446,186 @@ int kbe_render_video(const float* points, const float* image, const float* depth
                            2 * align16(4 * (size_t) sc0.tiles_x * sc0.tiles_y * CNT_STRIDE) / sizeof(int));
         if (int rc0 = launched("kbe_render_video/counters")) return rc0;
     }
-    hipEvent_t start = lanes > 1 || (ringed && ds[0] != cs) ? make() : nullptr;
+    hipEvent_t start = lanes > 1 || (ringed && dc != cs) ? make() : nullptr;
     // the other streams start once everything enqueued on `stream` so far (the cloud) is done
     if (start && ok) {
         (void) hipEventRecord(start, cs);
         for (int l = 1; l < lanes; l++) (void) hipStreamWaitEvent(ls[l], start, 0);
-        if (ringed && ds[0] != cs) (void) hipStreamWaitEvent(ds[0], start, 0);
+        if (ringed && dc != cs) (void) hipStreamWaitEvent(dc, start, 0);
     }
-    // which lane renders frame i with one frame per launch (render() below): whole groups of G = -batch consecutive frames when
-    // they are handed to pinned host memory per group, round-robin otherwise; a lane's frame count tells its LAST frame
-    const bool by_groups = batch < 0 && host_dev != nullptr;
-    // The transfer groups of the hand-off by groups: sizes 1, 2, 4, ... (KBE_VIDEO_FAST_RAMP: 1, 3, 7, ...) up to G = -batch, then G.  The link is idle until the
-    // first group has been rendered, and a transfer costs ~25 us whatever its size: a video of 20 frames in groups of 2 ran at
-    // 41 GB/s, in groups of 16 it would wait for 16 frames before the first byte moves.  Small groups first start the link
-    // after one frame; the groups double while it is busy.  Group g goes to lane g % lanes.
-    std::vector<int> group_start;                               // group_start[g] .. group_start[g + 1]: the frames of group g
-    if (by_groups) {
-        const int G = -batch;
-        for (int i0 = 0, size = (flags & KBE_VIDEO_EVEN_GROUPS) ? G : 1; i0 < n_frames; ) {
-            group_start.push_back(i0);
-            i0 += size < n_frames - i0 ? size : n_frames - i0;
-            const int grown = (flags & KBE_VIDEO_FAST_RAMP) ? size * 2 + 1 : size * 2;
-            size = grown < G ? grown : G;
-        }
-        group_start.push_back(n_frames);
-    }
-    const int n_groups = by_groups ? (int) group_start.size() - 1 : 0;
-    int lane_frames[KBE_MAX_LANES] = {}, lane_total[KBE_MAX_LANES] = {};
-    if (by_groups) for (int g = 0; g < n_groups; g++) lane_total[g % lanes] += group_start[g + 1] - group_start[g];
-    else for (int i = 0; i < n_frames; i++) lane_total[i % lanes]++;
-    auto render = [&](int i, int l, uint8_t* out) {
-        uint8_t* raw = stage + (size_t) l * fb;
-        const int fill_flags = lanes >= KBE_FILL_BY_COUNT_MIN_LANES ? (KBE_STAGE_FILL_BY_COUNT | ((flags & KBE_VIDEO_FILL_DIST) ? KBE_STAGE_FILL_DIST : 0)) : 0;
-        int rc;
-        if (packed)         // the fused scatter on the packed cloud; a lane's frames alternate between its two hole counters
-            rc = kbe_render_frame_fused(packed, N, cloud_focal, W, H, focals[i], baseline, shifts + 3 * (size_t) i,
-                                        (char*) scratch + (size_t) l * sb, crop ? raw : out, nullptr, nullptr, nullptr, nullptr,
-                                        KBE_STAGE_TILES | KBE_STAGE_FILL | fill_flags | ((flags & KBE_VIDEO_FUSED_LEAN) ? KBE_STAGE_FUSED_LEAN : 0) |
-                                        ((flags & KBE_VIDEO_FUSED_ROOMY) ? KBE_STAGE_FUSED_ROOMY : 0), crop ? rect : nullptr, lane_frames[l]++ & 1,
-                                        (kbe_stream_t) ls[l]);
-        else {
-            // a lane's frames alternate between the two z-buffers (A, B, A, ...), each clearing the other's in its tile
-            // launch; a lane's LAST frame, if it falls on A, takes the stand-alone form (A cleared by its fill launch), so
-            // that every call leaves A empty -- B is always cleared before it is used
-            // (the lane's last frame by COUNT: with groups of G frames per lane `i + lanes >= n_frames` named frames in the
-            // middle of a lane's share, which then ran stand-alone and left B dirty for the lane's next frame)
-            const int k = lane_frames[l]++;
-            const bool last_of_lane = k + 1 == lane_total[l];
-            const int zflags = (k & 1) ? KBE_STAGE_ZBUF_B : (last_of_lane ? 0 : KBE_STAGE_ZBUF_A);
-            rc = kbe_render_frame_stages(points, image, depth, N, W, H, focals[i], baseline, shifts + 3 * (size_t) i,
-                                         (char*) scratch + (size_t) l * sb, crop ? raw : out, nullptr, nullptr, nullptr, nullptr,
-                                         KBE_VIDEO_STAGES | fill_flags | zflags, crop ? rect : nullptr, raster_w, raster_n, (kbe_stream_t) ls[l]);
-        }
-        if (rc == KBE_OK && crop) rc = kbe_crop_resize_u8(raw, W, H, crop_w, crop_h, out, (kbe_stream_t) ls[l]);
-        return rc;
-    };
-    // up to `group` frames of lane l: each scattered into a scratch set of its own, filled together, cropped
+    const VideoPlan plan = plan_video(VideoPlanIn{ n_frames, lanes, group, batch, dest, fin, (flags & KBE_VIDEO_FAST_RAMP) != 0, (flags & KBE_VIDEO_EVEN_GROUPS) != 0,
+                                                   packed != nullptr, !(flags & KBE_VIDEO_NO_AHEAD) },
+                                      [&](int n, int n_next) { return fused_can_place_ahead(N, W, H, n, n_next); });
+
+    // ---- how a planned launch is enqueued: its frames scattered into scratch sets of their own, filled together, cropped
     static const FillDirs fill_dirs = make_fill_dirs();
-    int set_frames[KBE_MAX_LANES][KBE_FRAME_JOBS] = {}, set_total[KBE_MAX_LANES][KBE_FRAME_JOBS] = {};
-    bool counting = false;
-    // the calls of every lane in order (noted by the counting pass): the fused route's tile launch of a group also makes the
-    // placements of the lane's next group
-    struct GroupCall { int count; int idx[KBE_FRAME_JOBS]; };
-    std::vector<GroupCall> lane_calls[KBE_MAX_LANES];
-    size_t lane_pos[KBE_MAX_LANES] = {};
-    bool lane_placed[KBE_MAX_LANES] = {};
-    auto render_group = [&](int l, int count, const int* idx, uint8_t* const* outs) {
-        if (counting) {
-            GroupCall c = {};
-            c.count = count;
-            for (int j = 0; j < count; j++) { set_total[l][j]++; c.idx[j] = idx[j]; }
-            lane_calls[l].push_back(c);
-            return (int) KBE_OK;
+    const int in_flight = plan.single ? lanes : lanes * group;          // frames in flight
+    const int fill_flags = in_flight >= KBE_FILL_BY_COUNT_MIN_LANES ? (KBE_STAGE_FILL_BY_COUNT | ((flags & KBE_VIDEO_FILL_DIST) ? KBE_STAGE_FILL_DIST : 0)) : 0;
+    const int build = (flags & KBE_VIDEO_FUSED_LEAN) ? 1 : ((flags & KBE_VIDEO_FUSED_ROOMY) ? 2 : 0);
+    auto dst = [&](const PlanFrame& f) { return (dest == VideoDest::HBM ? host_out : ringed ? ring0 : finished) + (size_t) f.slot * fb; };
+    auto fused_target = [&](const PlanFrame& f, uint8_t* frame) {
+        char* const scr = (char*) scratch + (size_t) f.set * sb;
+        return FusedTarget{ make_camera(W, H, focals[f.frame], baseline, shifts + 3 * (size_t) f.frame), carve(scr, W, H), scratch_place(scr, W, H), f.turn & 1, frame,
+                            nullptr, nullptr, nullptr, nullptr, f.turn };
+    };
+    auto render = [&](const PlanLaunch& a) {
+        const hipStream_t s = ls[a.lane];
+        const PlanFrame* const fr = &plan.frames[a.first];
+        uint8_t* outs[KBE_FRAME_JOBS];
+        uint8_t* raws[KBE_FRAME_JOBS];          // where the frames are rendered: the lane's raw frames when cropped
+        for (int j = 0; j < a.count; j++) {
+            outs[j] = dst(fr[j]);
+            raws[j] = crop ? stage + (size_t) (KBE_FRAME_JOBS * a.lane + j) * fb : outs[j];
         }
-        const int fill_flags = (lanes * group >= KBE_FILL_BY_COUNT_MIN_LANES ? KBE_STAGE_FILL_BY_COUNT : 0) | ((flags & KBE_VIDEO_FILL_DIST) ? KBE_STAGE_FILL_DIST : 0);
-        uint8_t* raws[KBE_FRAME_JOBS];
         int rc = KBE_OK;
         if (!packed) {
-            // bucket route: every launch (projection, tiles, fill) takes the whole group
+            // bucket route: every launch (projection, tiles, fill) takes all the frames
             FrameJob jobs[KBE_FILL_JOBS];
-            for (int j = 0; j < count; j++) {
-                const int i = idx[j], k = set_frames[l][j]++;
-                const bool last_of_set = k + 1 == set_total[l][j];
-                raws[j] = stage + (size_t) (KBE_FRAME_JOBS * l + j) * fb;
-                jobs[j] = FrameJob{ focals[i], shifts + 3 * (size_t) i, (char*) scratch + (size_t) (group * l + j) * sb, crop ? raws[j] : outs[j], nullptr, nullptr,
-                                    nullptr, nullptr, (k & 1) ? KBE_STAGE_ZBUF_B : (last_of_set ? 0 : KBE_STAGE_ZBUF_A) };
-            }
-            rc = render_jobs(points, image, depth, N, W, H, baseline, count, jobs, KBE_VIDEO_STAGES | ((fill_flags & KBE_STAGE_FILL_BY_COUNT) ? fill_flags : 0),
-                             crop ? rect : nullptr, raster_w, raster_n, ls[l]);
+            for (int j = 0; j < a.count; j++)
+                jobs[j] = FrameJob{ focals[fr[j].frame], shifts + 3 * (size_t) fr[j].frame, (char*) scratch + (size_t) fr[j].set * sb, raws[j], nullptr, nullptr, nullptr, nullptr,
+                                    fr[j].zbuf == PLAN_ZBUF_A ? KBE_STAGE_ZBUF_A : (fr[j].zbuf == PLAN_ZBUF_B ? KBE_STAGE_ZBUF_B : 0) };
+            rc = render_jobs(points, image, depth, N, W, H, baseline, a.count, jobs, KBE_VIDEO_STAGES | fill_flags, crop ? rect : nullptr, raster_w, raster_n, s);
+        } else if (plan.single) {
+            // the fused scatter on the packed cloud, one frame on its own; a lane's frames alternate between its two hole counters
+            rc = kbe_render_frame_fused(packed, N, cloud_focal, W, H, focals[fr[0].frame], baseline, shifts + 3 * (size_t) fr[0].frame, (char*) scratch + (size_t) fr[0].set * sb,
+                                        raws[0], nullptr, nullptr, nullptr, nullptr, KBE_STAGE_TILES | KBE_STAGE_FILL | fill_flags |
+                                        ((flags & KBE_VIDEO_FUSED_LEAN) ? KBE_STAGE_FUSED_LEAN : 0) | ((flags & KBE_VIDEO_FUSED_ROOMY) ? KBE_STAGE_FUSED_ROOMY : 0),
+                                        crop ? rect : nullptr, fr[0].turn & 1, (kbe_stream_t) s);
         } else {
-            // fused route: the binning launch, the tile launch and the fill each take the whole group
+            // fused route: the binning launch and the tile launch take all the frames, the fill four at a time; the tile launch also
+            // makes the placements of the lane's next launch when the plan says so
+            FusedTarget ft[KBE_FRAME_JOBS], nt[KBE_FRAME_JOBS];
             FillTarget targets[KBE_FRAME_JOBS];
-            FusedTarget ft[KBE_FRAME_JOBS];
-            for (int j = 0; j < count; j++) {
-                const int i = idx[j], k = set_frames[l][j]++;
-                char* const scr = (char*) scratch + (size_t) (group * l + j) * sb;
-                raws[j] = stage + (size_t) (KBE_FRAME_JOBS * l + j) * fb;
-                uint8_t* const target = crop ? raws[j] : outs[j];
-                const Scratch sc = carve(scr, W, H);
-                ft[j] = FusedTarget{ make_camera(W, H, focals[i], baseline, shifts + 3 * (size_t) i), sc, scratch_place(scr, W, H), k & 1, target, nullptr, nullptr, nullptr, nullptr, k };
-                targets[j] = FillTarget{ sc, sc.hole_count + (k & 1), target, nullptr, 0, sc.hole_count + ((k & 1) ^ 1) };
+            for (int j = 0; j < a.count; j++) {
+                ft[j] = fused_target(fr[j], raws[j]);
+                targets[j] = FillTarget{ ft[j].sc, ft[j].sc.hole_count + (fr[j].turn & 1), raws[j], nullptr, 0, ft[j].sc.hole_count + ((fr[j].turn & 1) ^ 1) };
             }
-            if (count == 0) return rc;
-            // the lane's next group: its placements ride in this group's tile launch (set j then takes its next turn)
-            FusedTarget nt[KBE_FRAME_JOBS];
-            int n_next = 0;
-            const size_t pos = lane_pos[l]++;
-            // (not for a next group that is LARGER: that is the ramp of the transfer groups at the start of a delivered video,
-            // where the first frames should leave as early as they can -- a one-frame launch that also places four frames holds
-            // the first transfer back: --steps 20 14.1 k -> 13.4 k frames/s with it)
-            if (!(flags & KBE_VIDEO_NO_AHEAD) && pos + 1 < lane_calls[l].size() && lane_calls[l][pos + 1].count <= count &&
-                fused_can_place_ahead(N, W, H, count, lane_calls[l][pos + 1].count)) {
-                const GroupCall& nc = lane_calls[l][pos + 1];
-                n_next = nc.count;
-                for (int j = 0; j < n_next; j++) {
-                    const int i = nc.idx[j], k = set_frames[l][j];
-                    char* const scr = (char*) scratch + (size_t) (group * l + j) * sb;
-                    nt[j] = FusedTarget{ make_camera(W, H, focals[i], baseline, shifts + 3 * (size_t) i), carve(scr, W, H), scratch_place(scr, W, H), k & 1, nullptr, nullptr, nullptr, nullptr, nullptr, k };
-                }
-            }
-            launch_frames_fused(ls[l], count, packed, N, cloud_focal, ft, lane_placed[l], n_next, nt, (flags & KBE_VIDEO_FUSED_LEAN) ? 1 : ((flags & KBE_VIDEO_FUSED_ROOMY) ? 2 : 0), near_depth);
-            lane_placed[l] = n_next > 0;
+            const int n_next = a.next >= 0 ? plan.launches[a.next].count : 0;
+            for (int j = 0; j < n_next; j++) nt[j] = fused_target(plan.frames[plan.launches[a.next].first + j], nullptr);
+            launch_frames_fused(s, a.count, packed, N, cloud_focal, ft, a.placed, n_next, nt, build, near_depth);
             if ((rc = launched("kbe_render_video/scatter"))) return rc;
-            FillRect fr = { 0, 0, W - 1, H - 1 };
-            if (crop) { fr.x0 = rect[0]; fr.y0 = rect[1]; fr.x1 = rect[2]; fr.y1 = rect[3]; }
-            for (int j0 = 0; j0 < count; j0 += KBE_FILL_JOBS)
-                launch_fill(ls[l], count - j0 < KBE_FILL_JOBS ? count - j0 : KBE_FILL_JOBS, targets + j0, W, H,
-                            KBE_STAGE_FILL | ((fill_flags & KBE_STAGE_FILL_BY_COUNT) ? fill_flags : 0), fill_dirs, fr, targets[0].sc.tiles_x * targets[0].sc.tiles_y);
+            const FillRect fr_rect = { rect[0], rect[1], rect[2], rect[3] };
+            for (int j0 = 0; j0 < a.count; j0 += KBE_FILL_JOBS)
+                launch_fill(s, a.count - j0 < KBE_FILL_JOBS ? a.count - j0 : KBE_FILL_JOBS, targets + j0, W, H, KBE_STAGE_FILL | fill_flags, fill_dirs, fr_rect,
+                            targets[0].sc.tiles_x * targets[0].sc.tiles_y);
             rc = launched("kbe_render_video/fill");
         }
-        for (int j0 = 0; j0 < count && rc == KBE_OK && crop; j0 += KBE_FILL_JOBS)
-            rc = crop_resize_group(count - j0 < KBE_FILL_JOBS ? count - j0 : KBE_FILL_JOBS, raws + j0, W, H, crop_w, crop_h, outs + j0, ls[l]);
+        for (int j0 = 0; j0 < a.count && rc == KBE_OK && crop; j0 += KBE_FILL_JOBS)
+            rc = crop_resize_group(a.count - j0 < KBE_FILL_JOBS ? a.count - j0 : KBE_FILL_JOBS, raws + j0, W, H, crop_w, crop_h, outs + j0, s);
         return rc;
     };
-    // whoever synchronises `stream` afterwards also sees every frame delivered and every other stream idle
-    auto join = [&]() {
-        for (int l = 1; l < lanes && ok; l++) { hipEvent_t e = make(); if (e) { (void) hipEventRecord(e, ls[l]); (void) hipStreamWaitEvent(cs, e, 0); } }
-        if (ringed && ds[0] != cs && ok) { hipEvent_t e = make(); if (e) { (void) hipEventRecord(e, ds[0]); (void) hipStreamWaitEvent(cs, e, 0); } }
-    };
-    int rc = KBE_OK;
+
+    // ---- the hand-off, by destination (HBM: none).  PER_FRAME: k_deliver behind every frame in the lane's own stream; GROUPS: a
+    // transfer group rendered by ONE lane into its slots leaves through an SDMA engine, or with one runtime transfer (hipMemcpyAsync)
+    // between a gate kernel that waits for the turn and one that passes it on; RING: a half is copied to the host with ONE runtime
+    // transfer on the copy stream while the other half is being rendered, cross-stream events per half, not per frame.
+    // (where the rendering binds, not the link, the transfers need no order: a lane that waits for its turn only idles)
+    DeliverCtl* const ctl_turns = host_dev && lanes > 1 && !(flags & KBE_VIDEO_FREE_TRANSFERS) ? (DeliverCtl*) (stage + ctl_offset) : nullptr;
+    // KBE_VIDEO_SDMA: the groups leave through an SDMA engine (above); whatever keeps HSA from it falls back to the runtime's
+    // transfers, group by group.  (Opened behind the first group's launches: the queries cost the host 10-25 us, which would
+    // otherwise sit in front of the video's first kernel.)
     SdmaCall sdma;
-    if (!ringed && !per_frame) {
-        // host_out is device memory: the last kernel of every frame stores straight into it (the frames stay in HBM)
-        if (pairs) {
-            // a chunk of group * lanes CONSECUTIVE frames at a time, lane l taking frames base + l * group .. base + l * group + group - 1 of
-            // it (consecutive cameras share candidate lists, kbe_fused.hip: share_plan; until round 5 lane l took frames l, l + lanes,
-            // ...: cameras `lanes` steps apart in every launch).  The last, partial chunk fills the lanes one after the other, `group`
-            // frames each.  (ADVICE r5 proposed to deal it evenly, ceil(remaining / lanes) frames per lane, so that every lane has work:
-            // measured in round 6 -- tools/batches/gpu_r06_tail.sh, frames/s left in HBM, lane by lane / evenly: 6 frames 26.5 / 26.4 k, 8: 29.5 /
-            // 29.5, 12: 33.5 / 33.4, 20: 35.9 / 33.9, 24: 37.6 / 35.5, 30: 38.2 / 37.7, 40: 39.8 / 39.6 -- never faster, 5 % slower
-            // where it turns one four-frame launch into four one-frame launches: a launch's ramp and tail cost more than the idle lanes.)
-            // (A first pass counts the frames of every scratch set: the bucket route must know a set's last frame.)
-            for (int pass = 0; pass < 2 && rc == KBE_OK; pass++) {
-                counting = pass == 0;
-                for (int base = 0; base < n_frames && rc == KBE_OK; base += group * lanes)
-                    for (int l = 0; l < lanes && rc == KBE_OK; l++) {
-                        int idx[KBE_FRAME_JOBS], count = 0;
-                        uint8_t* outs[KBE_FRAME_JOBS];
-                        for (int m = 0; m < group; m++) {
-                            const int i = KBE_HBM_CONSECUTIVE ? base + l * group + m : base + m * lanes + l;
-                            if (i < n_frames) { idx[count] = i; outs[count++] = host_out + (size_t) i * fb; }
-                        }
-                        if (count) rc = render_group(l, count, idx, outs);
-                    }
-            }
-        } else
-        for (int i = 0; i < n_frames && rc == KBE_OK; i++) rc = render(i, i % lanes, host_out + (size_t) i * fb);
-    } else if (!ringed) {
-        // Hand-off to pinned host memory in the lane's own stream (no event), the lanes taking turns:
-        //   batch == 0   per frame, k_deliver (a lane alternates between two finished-frame slots);
-        //   batch < 0    per group of G = -batch consecutive frames, rendered by ONE lane into its G slots and sent with one
-        //                runtime transfer (hipMemcpyAsync) between a gate kernel that waits for the turn and one that
-        //                passes it on.
-        // (where the rendering binds, not the link, the transfers need no order: a lane that waits for its turn only idles)
-        DeliverCtl* const ctl_turns = lanes > 1 && !(flags & KBE_VIDEO_FREE_TRANSFERS) ? (DeliverCtl*) (stage + ctl_offset) : nullptr;
-        DeliverCtl* ctl = ctl_turns;
-        if (batch == 0) {
-            for (int i = 0; i < n_frames && rc == KBE_OK; i++) {
-                const int l = i % lanes, slot = i % slots;
-                uint8_t* out = finished + (size_t) slot * fb;
-                rc = render(i, l, out);
-                if (rc != KBE_OK) break;
-                hipLaunchKernelGGL(k_deliver, dim3(DELIVER_BLOCKS), dim3(DELIVER_THREADS), 0, ls[l], out, host_dev + (size_t) i * fb, fb,
-                                   ctl, (uint32_t) i);
-                rc = launched("kbe_render_video/deliver");
-            }
-        } else {
-            const int G = -batch;
-            // KBE_VIDEO_SDMA: the groups leave through an SDMA engine (above); whatever keeps HSA from it falls back to the runtime's
-            // transfers, group by group
-            // (opened behind the first group's launches, below: the queries cost the host 10-25 us, which would otherwise sit in front of
-            // the video's first kernel)
-            bool sdma_asked = !(flags & KBE_VIDEO_SDMA);
-            volatile int64_t* lane_fin[KBE_MAX_LANES] = {};         // the completion signal of the group the lane's slots hold
-            // how long a group may wait for its turn: the transfers of every other lane in front of it (a poll is ~1 us; the
-            // link moves ~50 bytes per ns), three times over -- a fixed 4 ms was no margin for 16 frames of 2048^2 (3.8 ms each)
-            const double group_us = (double) G * (double) fb / 50.0e3;
-            const int turn_polls = (int) fmin(fmax(3.0 * lanes * group_us, (double) DELIVER_MAX_POLLS), 1.0e6);
-            if (pairs) {                                                // the frames of every scratch set, counted first
-                counting = true;
-                for (int g = 0; g < n_groups; g++) {
-                    const int l = g % lanes, nb = group_start[g + 1] - group_start[g];
-                    for (int k = 0; k < nb; k += group) {
-                        int idx[KBE_FRAME_JOBS], count = 0;
-                        for (int m = 0; m < group && k + m < nb; m++) idx[count++] = group_start[g] + k + m;
-                        (void) render_group(l, count, idx, nullptr);
-                    }
-                }
-                counting = false;
-            }
-#if defined(KBE_VIDEO_GPU_TRACE)     // dev build only (tools/handoff_gpu_trace.py): when, on the device, a group's frames are ready, its gate opens, its transfer ends
-            std::vector<hipEvent_t> ev_begin(n_groups), ev_ready(n_groups), ev_gate(n_groups), ev_copied(n_groups);
-            hipEvent_t ev_start;
-            (void) hipEventCreate(&ev_start);
-            (void) hipEventRecord(ev_start, cs);
-            for (int g = 0; g < n_groups; g++) { (void) hipEventCreate(&ev_begin[g]); (void) hipEventCreate(&ev_ready[g]); (void) hipEventCreate(&ev_gate[g]); (void) hipEventCreate(&ev_copied[g]); }
-#endif
-            for (int g = 0; g < n_groups && rc == KBE_OK; g++) {
-                const int l = g % lanes, i0 = group_start[g], nb = group_start[g + 1] - i0;
-#if defined(KBE_VIDEO_GPU_TRACE)
-                (void) hipEventRecord(ev_begin[g], ls[l]);
-#endif
-#if defined(KBE_VIDEO_TRACE)
-                const double t_g = trace_now();
-#endif
-                uint8_t* base = finished + (size_t) l * fin * fb;
-                // (SDMA: the lane's slots hold the group it sent last -- until that has left.  Two sets of slots per lane, so that a
-                // lane renders its next group while its last one leaves, measured SLOWER: 14.2 k instead of 14.6 k frames/s for 20
-                // frames, 15.9 k instead of 16.6 k for 75 -- a lane then renders the group after next while the other lane still
-                // renders the group the engine waits for)
-                if (lane_fin[l]) { hipLaunchKernelGGL(k_signal_wait, dim3(1), dim3(64), 0, ls[l], lane_fin[l], sdma_pool().wait_ticks, sdma_pool().gave_up); lane_fin[l] = nullptr; }
-                if (pairs) for (int k = 0; k < nb && rc == KBE_OK; k += group) {
-                    int idx[KBE_FRAME_JOBS], count = 0;
-                    uint8_t* outs[KBE_FRAME_JOBS];
-                    for (int m = 0; m < group && k + m < nb; m++) { idx[count] = i0 + k + m; outs[count++] = base + (size_t) (k + m) * fb; }
-                    rc = render_group(l, count, idx, outs);
-                }
-                else for (int k = 0; k < nb && rc == KBE_OK; k++) rc = render(i0 + k, l, base + (size_t) k * fb);
-                if (rc != KBE_OK) break;
-#if defined(KBE_VIDEO_TRACE)     // dev build only (tools/handoff_trace.py): where does the host spend the call?
-                const double t_r = trace_now();
-#endif
-#if defined(KBE_VIDEO_GPU_TRACE)
-                (void) hipEventRecord(ev_ready[g], ls[l]);
-#endif
-                if (!sdma_asked) {
-                    sdma_asked = true;
-                    (void) sdma_open(sdma, stage, host_out);
-                }
-                // the engine takes the copies in order: no turns -- while it takes them (a copy it refuses sends the rest of the video
-                // through the runtime's transfers, which take turns again: ADVICE r5)
-                ctl = sdma.ok ? nullptr : ctl_turns;
-                if (ctl) hipLaunchKernelGGL(k_turn, dim3(1), dim3(64), 0, ls[l], ctl, 0, turn_polls);
-#if defined(KBE_VIDEO_GPU_TRACE)
-                (void) hipEventRecord(ev_gate[g], ls[l]);
-#endif
-#if defined(KBE_VIDEO_TRACE)
-                const double t_t = trace_now();
-#endif
-                bool sent = false;
-                if (sdma.ok) {
-                    SdmaPair p;
-                    const bool paired = sdma_pair(sdma, p);
-                    if (paired && hsa_amd_memory_async_copy_on_engine(host_out + (size_t) i0 * fb, sdma.cpu, base, sdma.gpu, (size_t) nb * fb, 1, &p.dep, p.fin,
-                                                                      sdma.engine[sdma.sent++ & 1], true) == HSA_STATUS_SUCCESS) {
-                        // the copy is on the engine and waits for its release: from here on an error must go through sdma_abort
-                        const bool inject = (flags & KBE_VIDEO_INJECT_FAULT) && g == (n_groups > 1 ? 1 : 0);
-                        if (!inject) hipLaunchKernelGGL(k_signal_release, dim3(1), dim3(64), 0, ls[l], p.dep_value);
-                        const hipError_t le = inject ? hipErrorLaunchFailure : hipGetLastError();
-                        if (le != hipSuccess) { rc = fail(KBE_E_LAUNCH, inject ? "kbe_render_video: injected hand-off fault (KBE_VIDEO_INJECT_FAULT)" : "kbe_render_video/release", le); break; }
-                        sdma.used.back().released = true;
-                        lane_fin[l] = p.fin_value;
-                        sent = true;
-                    } else {
-                        // this group and the rest: the runtime's transfers (the pair, if there is one, was never handed to the engine: idle again)
-                        if (paired) { std::lock_guard<std::mutex> lock(sdma_pool().mu); sdma_pool().idle.push_back(sdma.used.back()); sdma.used.pop_back(); }
-                        sdma.ok = false;
-                        if (ctl_turns && !ctl) { ctl = ctl_turns; hipLaunchKernelGGL(k_turn, dim3(1), dim3(64), 0, ls[l], ctl, 0, turn_polls); }
-                    }
-                }
-                const hipError_t e = sent ? hipSuccess : hipMemcpyAsync(host_out + (size_t) i0 * fb, base, (size_t) nb * fb, hipMemcpyDeviceToHost, ls[l]);
-                if (e != hipSuccess) { rc = fail(KBE_E_LAUNCH, "kbe_render_video: hipMemcpyAsync", e); break; }
-#if defined(KBE_VIDEO_GPU_TRACE)
-                (void) hipEventRecord(ev_copied[g], ls[l]);
-#endif
-#if defined(KBE_VIDEO_TRACE)
-                const double t_c = trace_now();
-#endif
-                if (ctl) hipLaunchKernelGGL(k_turn, dim3(1), dim3(64), 0, ls[l], ctl, 1, 0);
-                rc = launched("kbe_render_video/turn");
-#if defined(KBE_VIDEO_TRACE)
-                fprintf(stderr, "group %3d lane %d frames %3d..%3d: t=%8.1f us  render-enqueue %7.1f  turn %6.1f  hipMemcpyAsync %7.1f  turn %6.1f\n", g, l, i0, i0 + nb - 1,
-                        (t_g - t_call) * 1e6, (t_r - t_g) * 1e6, (t_t - t_r) * 1e6, (t_c - t_t) * 1e6, (trace_now() - t_c) * 1e6);
-#endif
-            }
-            // (SDMA) a lane is done when its last group has left: whoever waits for the lanes (join) waits for the frames
-            for (int l = 0; l < lanes; l++)
-                if (lane_fin[l] && rc == KBE_OK)            // (KBE_VIDEO_INJECT_TIMEOUT: one tick of patience -- the give-up path, for its test)
-                    hipLaunchKernelGGL(k_signal_wait, dim3(1), dim3(64), 0, ls[l], lane_fin[l], (flags & KBE_VIDEO_INJECT_TIMEOUT) ? 1ull : sdma_pool().wait_ticks, sdma_pool().gave_up);
-#if defined(KBE_VIDEO_GPU_TRACE)
-            for (int l = 0; l < lanes; l++) (void) hipStreamSynchronize(ls[l]);
-            for (int g = 0; g < n_groups && rc == KBE_OK; g++) {
-                float b = 0, r = 0, o = 0, c = 0;
-                (void) hipEventElapsedTime(&b, ev_start, ev_begin[g]); (void) hipEventElapsedTime(&r, ev_start, ev_ready[g]);
-                (void) hipEventElapsedTime(&o, ev_start, ev_gate[g]); (void) hipEventElapsedTime(&c, ev_start, ev_copied[g]);
-                fprintf(stderr, "group %3d lane %d frames %3d..%3d: render %8.1f .. %8.1f us, gate open %8.1f, transfer ends %8.1f (%.1f GB/s from the gate)\n", g, g % lanes,
-                        group_start[g], group_start[g + 1] - 1, b * 1e3, r * 1e3, o * 1e3, c * 1e3, (double) (group_start[g + 1] - group_start[g]) * fb / ((c - o) * 1e6));
-            }
-#endif
-        }
-    } else {
-        // staged ring: a half is copied to the host with ONE runtime transfer while the other half is being rendered;
-        // cross-stream events are per batch, not per frame
-        const hipStream_t dc = ds[0];
-        hipEvent_t rendered[2][KBE_MAX_LANES] = {}, copied[2] = { nullptr, nullptr };
-        for (int h = 0; h < 2; h++) {
-            copied[h] = make();
-            for (int l = 0; l < lanes; l++) if (ls[l] != dc) rendered[h][l] = make();
-        }
-        int n_batches = 0;
-        for (int i0 = 0; i0 < n_frames && rc == KBE_OK && ok; i0 += batch, n_batches++) {
-            const int half = n_batches & 1;
-            const int nb = n_frames - i0 < batch ? n_frames - i0 : batch;
-            if (n_batches >= 2)
-                for (int l = 0; l < lanes; l++) if (ls[l] != dc) (void) hipStreamWaitEvent(ls[l], copied[half], 0);    // the half is free again
-            for (int k = 0; k < nb && rc == KBE_OK; k++) rc = render(i0 + k, (i0 + k) % lanes, ring[half] + (size_t) k * fb);
-            if (rc != KBE_OK) break;
-            for (int l = 0; l < lanes; l++) {
-                if (ls[l] == dc) continue;                                  // same stream as the transfer: ordered anyway
-                (void) hipEventRecord(rendered[half][l], ls[l]);
-                (void) hipStreamWaitEvent(dc, rendered[half][l], 0);
-            }
-            const hipError_t e = hipMemcpyAsync(host_out + (size_t) i0 * fb, ring[half], (size_t) nb * fb, hipMemcpyDeviceToHost, dc);
-            if (e != hipSuccess) { rc = fail(KBE_E_LAUNCH, "kbe_render_video: hipMemcpyAsync", e); break; }
-            (void) hipEventRecord(copied[half], dc);
-        }
+    bool sdma_asked = !(flags & KBE_VIDEO_SDMA);
+    volatile int64_t* lane_fin[KBE_MAX_LANES] = {};         // the completion signal of the group the lane's slots hold
+    // how long a group may wait for its turn: the transfers of every other lane in front of it (a poll is ~1 us; the
+    // link moves ~50 bytes per ns), three times over -- a fixed 4 ms was no margin for 16 frames of 2048^2 (3.8 ms each)
+    const double group_us = (double) -batch * (double) fb / 50.0e3;
+    const int turn_polls = (int) fmin(fmax(3.0 * lanes * group_us, (double) DELIVER_MAX_POLLS), 1.0e6);
+    hipEvent_t rendered[2][KBE_MAX_LANES] = {}, copied[2] = { nullptr, nullptr };
+    for (int h = 0; h < 2 && ringed; h++) {
+        copied[h] = make();
+        for (int l = 0; l < lanes; l++) if (ls[l] != dc) rendered[h][l] = make();
     }
+    if (dest == VideoDest::GROUPS) trace.start((int) plan.units.size(), cs);
+    // wait until the unit's slots are free
+    auto wait = [&](int u, const PlanUnit& un) {
+        if (dest == VideoDest::GROUPS) {
+            trace.begin(u, ls[un.lane]);
+            // (SDMA: the lane's slots hold the group it sent last -- until that has left.  Two sets of slots per lane, so that a
+            // lane renders its next group while its last one leaves, measured SLOWER: 14.2 k instead of 14.6 k frames/s for 20
+            // frames, 15.9 k instead of 16.6 k for 75 -- a lane then renders the group after next while the other lane still
+            // renders the group the engine waits for)
+            if (lane_fin[un.lane]) hipLaunchKernelGGL(k_signal_wait, dim3(1), dim3(64), 0, ls[un.lane], lane_fin[un.lane], sdma_pool().wait_ticks, sdma_pool().gave_up);
+            lane_fin[un.lane] = nullptr;
+        } else if (ringed && u >= 2) {
+            for (int l = 0; l < lanes; l++) if (ls[l] != dc) (void) hipStreamWaitEvent(ls[l], copied[u & 1], 0);    // the half is free again
+        }
+    };
+    // a transfer group: its frames leave through the engine or the runtime's transfer, the lanes taking turns on the link
+    auto send_group = [&](int u, const PlanUnit& un) -> int {
+        const hipStream_t s = ls[un.lane];
+        uint8_t* const base = finished + (size_t) un.lane * fin * fb;
+        const size_t bytes = (size_t) un.count * fb;
+        trace.ready(u, s);
+        if (!sdma_asked) { sdma_asked = true; (void) sdma_open(sdma, stage, host_out); }
+        // the engine takes the copies in order: no turns -- while it takes them (a copy it refuses sends the rest of the video
+        // through the runtime's transfers, which take turns again: ADVICE r5)
+        DeliverCtl* ctl = sdma.ok ? nullptr : ctl_turns;
+        if (ctl) hipLaunchKernelGGL(k_turn, dim3(1), dim3(64), 0, s, ctl, 0, turn_polls);
+        trace.gate(u, s);
+        bool sent = false;
+        if (sdma.ok) {
+            SdmaPair p;
+            const bool paired = sdma_pair(sdma, p);
+            if (paired && hsa_amd_memory_async_copy_on_engine(host_out + (size_t) un.first * fb, sdma.cpu, base, sdma.gpu, bytes, 1, &p.dep, p.fin,
+                                                              sdma.engine, true) == HSA_STATUS_SUCCESS) {
+                // the copy is on the engine and waits for its release: from here on an error must go through sdma_abort
+                const bool inject = (flags & KBE_VIDEO_INJECT_FAULT) && u == (plan.units.size() > 1 ? 1 : 0);
+                if (!inject) hipLaunchKernelGGL(k_signal_release, dim3(1), dim3(64), 0, s, p.dep_value);
+                const hipError_t le = inject ? hipErrorLaunchFailure : hipGetLastError();
+                if (le != hipSuccess) return fail(KBE_E_LAUNCH, inject ? "kbe_render_video: injected hand-off fault (KBE_VIDEO_INJECT_FAULT)" : "kbe_render_video/release", le);
+                sdma.used.back().released = true;
+                lane_fin[un.lane] = p.fin_value;
+                sent = true;
+            } else {
+                // this group and the rest: the runtime's transfers (the pair, if there is one, was never handed to the engine: idle again)
+                if (paired) { std::lock_guard<std::mutex> lock(sdma_pool().mu); sdma_pool().idle.push_back(sdma.used.back()); sdma.used.pop_back(); }
+                sdma.ok = false;
+                if (ctl_turns && !ctl) { ctl = ctl_turns; hipLaunchKernelGGL(k_turn, dim3(1), dim3(64), 0, s, ctl, 0, turn_polls); }
+            }
+        }
+        const hipError_t e = sent ? hipSuccess : hipMemcpyAsync(host_out + (size_t) un.first * fb, base, bytes, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return fail(KBE_E_LAUNCH, "kbe_render_video: hipMemcpyAsync", e);
+        trace.copied(u, s);
+        if (ctl) hipLaunchKernelGGL(k_turn, dim3(1), dim3(64), 0, s, ctl, 1, 0);
+        const int rc = launched("kbe_render_video/turn");
+        trace.sent(u, un);
+        return rc;
+    };
+    // send the unit after its launches
+    auto send = [&](int u, const PlanUnit& un) -> int {
+        switch (dest) {
+        case VideoDest::PER_FRAME:
+            hipLaunchKernelGGL(k_deliver, dim3(DELIVER_BLOCKS), dim3(DELIVER_THREADS), 0, ls[un.lane], dst(plan.frames[plan.launches[un.launch0].first]),
+                               host_dev + (size_t) un.first * fb, fb, ctl_turns, (uint32_t) un.first);
+            return launched("kbe_render_video/deliver");
+        case VideoDest::GROUPS: return send_group(u, un);
+        case VideoDest::RING: {
+            const int h = u & 1;
+            for (int l = 0; l < lanes; l++)
+                if (ls[l] != dc) { (void) hipEventRecord(rendered[h][l], ls[l]); (void) hipStreamWaitEvent(dc, rendered[h][l], 0); }    // (same stream: ordered anyway)
+            const hipError_t e = hipMemcpyAsync(host_out + (size_t) un.first * fb, ring0 + (size_t) h * batch * fb, (size_t) un.count * fb, hipMemcpyDeviceToHost, dc);
+            if (e != hipSuccess) return fail(KBE_E_LAUNCH, "kbe_render_video: hipMemcpyAsync", e);
+            (void) hipEventRecord(copied[h], dc);
+            return KBE_OK;
+        }
+        default: return KBE_OK;             // HBM: the last kernel of every frame stored straight into host_out
+        }
+    };
+
+    // ---- the plan, in order
+    int rc = KBE_OK;
+    for (int u = 0; u < (int) plan.units.size() && rc == KBE_OK && ok; u++) {
+        const PlanUnit& un = plan.units[u];
+        wait(u, un);
+        for (int a = un.launch0; a < un.launch1 && rc == KBE_OK; a++) rc = render(plan.launches[a]);
+        if (rc == KBE_OK) rc = send(u, un);
+    }
+    // drain: (SDMA) a lane is done when its last group has left -- whoever waits for the lanes (join) waits for the frames
+    for (int l = 0; l < lanes; l++)
+        if (lane_fin[l] && rc == KBE_OK)            // (KBE_VIDEO_INJECT_TIMEOUT: one tick of patience -- the give-up path, for its test)
+            hipLaunchKernelGGL(k_signal_wait, dim3(1), dim3(64), 0, ls[l], lane_fin[l], (flags & KBE_VIDEO_INJECT_TIMEOUT) ? 1ull : sdma_pool().wait_ticks, sdma_pool().gave_up);
+    if (dest == VideoDest::GROUPS) trace.finish(plan, ls, lanes, fb, rc);
     if (rc != KBE_OK) sdma_abort(sdma, ls, lanes);       // no copy of a failed call outlives it, none keeps waiting for its release
     join();
     sdma_close(sdma, cs);
