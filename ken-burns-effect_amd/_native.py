@@ -185,6 +185,21 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _rect(fill_rect):
+    return None if fill_rect is None else (ctypes.c_int * 4)(*[int(v) for v in fill_rect])
+
+
+def _group_args(cameras, scratch, stride, out=None, fill_rect=None):
+    """The argument arrays of a group of frames [(focal, shift3)], frame k on scratch set k: (focals, shifts, set pointers,
+    frame pointers -- None without `out` --, fill rectangle)."""
+    n = len(cameras)
+    focals = (ctypes.c_double * n)(*[float(c[0]) for c in cameras])
+    shifts = (ctypes.c_float * (3 * n))(*[float(v) for c in cameras for v in c[1]])
+    sets = (ctypes.c_void_p * n)(*[scratch.data_ptr() + k * stride for k in range(n)])
+    frames = None if out is None else (ctypes.c_void_p * n)(*[out[k].data_ptr() for k in range(n)])
+    return focals, shifts, sets, frames, _rect(fill_rect)
+
+
 def fused_build_bits(video=False):
     """KBE_FUSED_CAP=lean|roomy (tests, measurements): the flag that forces one build of the fused route's tile launches
     (KBE_STAGE_FUSED_LEAN / _ROOMY, or the kbe_render_video form).  The environment is read HERE, per call; the library reads none."""
@@ -199,10 +214,6 @@ HANDOFF_DEFAULT = 'sdma'    # measured (profiles/r05_handoff_sdma.txt): 20 frame
 def handoff_by_sdma():
     """Do a delivered video's frame groups leave through an SDMA engine (KBE_VIDEO_SDMA) or through hipMemcpyAsync (a blit kernel)?"""
     return os.environ.get('KBE_HANDOFF', HANDOFF_DEFAULT) == 'sdma'
-
-
-def stride_of(K, state):
-    return int(K.lib.kbe_video_scratch_stride(_i(state['W']), _i(state['H']), _i(state['N'])))
 
 
 class HipKernels:
@@ -412,7 +423,7 @@ class HipKernels:
         ``stages``: bit 1 = projection launch (bucket path only), 2 = scatter / tile launch, 4 = hole fill (+ flags).
         ``parity`` (fused route, include/kbe.h): -1 = a frame on its own; 0, 1, 0, ... for consecutive frames on one scratch."""
         frame = state['frame'] if out is None else out
-        rect = None if fill_rect is None else (ctypes.c_int * 4)(*[int(v) for v in fill_rect])
+        rect = _rect(fill_rect)
         if state.get('fused') if fused is None else fused:
             self._pack(state)
             self._check(self.lib.kbe_render_frame_fused(_ptr(state['packed'], torch.uint8), _i(state['N']), _d(state['cloud_focal']),
@@ -440,17 +451,18 @@ class HipKernels:
                                                              _stream()), 'kbe_frame_scratch_init_sets')
         return state['scratch_groups'], stride
 
+    def _group_sets(self, state, *counts):
+        """group_scratch for groups of `counts` frames that keeps the sets already held (four on first use)."""
+        held = state['scratch_groups'].numel() // self.scratch_stride(state) if 'scratch_groups' in state else 4
+        return self.group_scratch(state, max(*counts, held))
+
     def render_frame_group(self, state, cameras, baseline, out, stages=7, zbuf_flags=None, fill_rect=None):
         """kbe_render_frame_group: the launches of 1..4 frames [(focal, shift3)] of the bucket route, every launch taking all of
         them; out: uint8 [n,H,W,3] on the device.  Each frame uses a scratch set of its own (state['scratch_groups'])."""
         n = len(cameras)
         scratch, stride = self.group_scratch(state, max(n, 4))
-        focals = (ctypes.c_double * n)(*[float(c[0]) for c in cameras])
-        shifts = (ctypes.c_float * (3 * n))(*[float(v) for c in cameras for v in c[1]])
-        sets = (ctypes.c_void_p * n)(*[scratch.data_ptr() + k * stride for k in range(n)])
-        frames = (ctypes.c_void_p * n)(*[out[k].data_ptr() for k in range(n)])
+        focals, shifts, sets, frames, rect = _group_args(cameras, scratch, stride, out, fill_rect)
         zf = None if zbuf_flags is None else (ctypes.c_int * n)(*[int(v) for v in zbuf_flags])
-        rect = None if fill_rect is None else (ctypes.c_int * 4)(*[int(v) for v in fill_rect])
         self._check(self.lib.kbe_render_frame_group(_ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), _i(state['N']), _i(state['W']),
                                                     _i(state['H']), _d(float(baseline)), _i(n), focals, shifts, sets, frames, zf, _i(int(stages)), rect,
                                                     _i(state['raster_w']), _i(state['raster_n']), _stream()), 'kbe_render_frame_group')
@@ -460,13 +472,9 @@ class HipKernels:
         """kbe_render_frame_group_fused: the same on the packed cloud (k_place + k_frame + fill, each taking all the frames)."""
         n = len(cameras)
         self._pack(state)
-        scratch, stride = self.group_scratch(state, max(n, 4) if 'scratch_groups' not in state else max(n, state['scratch_groups'].numel() // stride_of(self, state)))
-        focals = (ctypes.c_double * n)(*[float(c[0]) for c in cameras])
-        shifts = (ctypes.c_float * (3 * n))(*[float(v) for c in cameras for v in c[1]])
-        sets = (ctypes.c_void_p * n)(*[scratch.data_ptr() + k * stride for k in range(n)])
-        frames = (ctypes.c_void_p * n)(*[out[k].data_ptr() for k in range(n)])
+        scratch, stride = self._group_sets(state, n)
+        focals, shifts, sets, frames, rect = _group_args(cameras, scratch, stride, out, fill_rect)
         par = None if parities is None else (ctypes.c_int * n)(*[int(v) for v in parities])
-        rect = None if fill_rect is None else (ctypes.c_int * 4)(*[int(v) for v in fill_rect])
         self._check(self.lib.kbe_render_frame_group_fused(_ptr(state['packed'], torch.uint8), _i(state['N']), _d(state['cloud_focal']), _i(state['W']),
                                                           _i(state['H']), _d(float(baseline)), _i(n), focals, shifts, sets, frames, par, _i(int(stages) | fused_build_bits()), rect,
                                                           _stream()), 'kbe_render_frame_group_fused')
@@ -479,20 +487,14 @@ class HipKernels:
         n = len(cameras)
         m = len(next_cameras) if next_cameras else 0
         self._pack(state)
-        scratch, stride = self.group_scratch(state, max(n, m, 4) if 'scratch_groups' not in state else max(n, m, state['scratch_groups'].numel() // stride_of(self, state)))
-
-        def arrays(cams, k):
-            return ((ctypes.c_double * k)(*[float(c[0]) for c in cams]), (ctypes.c_float * (3 * k))(*[float(v) for c in cams for v in c[1]]),
-                    (ctypes.c_void_p * k)(*[scratch.data_ptr() + j * stride for j in range(k)]))
-        focals, shifts, sets = arrays(cameras, n)
-        nf, ns, nsets = arrays(next_cameras, m) if m else (None, None, None)
-        frames = (ctypes.c_void_p * n)(*[out[k].data_ptr() for k in range(n)])
+        scratch, stride = self._group_sets(state, n, m)
+        focals, shifts, sets, frames, rect = _group_args(cameras, scratch, stride, out, fill_rect)
+        nf, ns, nsets = _group_args(next_cameras, scratch, stride)[:3] if m else (None, None, None)
         turn = [int(turn)] * n if isinstance(turn, int) else [int(t) for t in turn]
         if next_turn is None:
             next_turn = [(turn[k] if k < n else turn[0]) + 1 for k in range(m)]
         turns = (ctypes.c_int * n)(*turn)
         nturns = (ctypes.c_int * m)(*[int(t) for t in next_turn]) if m else None
-        rect = None if fill_rect is None else (ctypes.c_int * 4)(*[int(v) for v in fill_rect])
         self._check(self.lib.kbe_render_frame_group_ahead(_ptr(state['packed'], torch.uint8), _i(state['N']), _d(state['cloud_focal']), _i(state['W']),
                                                           _i(state['H']), _d(float(baseline)), _i(n), focals, shifts, sets, frames, turns, _i(1 if placed else 0),
                                                           _i(m), nf, ns, nsets, nturns, _i(int(stages) | fused_build_bits()), rect, _d(self.near_depth(state)), _stream()), 'kbe_render_frame_group_ahead')
@@ -505,14 +507,9 @@ class HipKernels:
         GPU works on the launch, and a measurement through the ordinary wrapper then reads the host's speed."""
         n, m = len(cameras), len(next_cameras)
         self._pack(state)
-        scratch, stride = self.group_scratch(state, max(n, m, 4) if 'scratch_groups' not in state else max(n, m, state['scratch_groups'].numel() // stride_of(self, state)))
-
-        def arrays(cams, k):
-            return ((ctypes.c_double * k)(*[float(c[0]) for c in cams]), (ctypes.c_float * (3 * k))(*[float(v) for c in cams for v in c[1]]),
-                    (ctypes.c_void_p * k)(*[scratch.data_ptr() + j * stride for j in range(k)]))
-        focals, shifts, sets = arrays(cameras, n)
-        nf, ns, nsets = arrays(next_cameras, m)
-        frames = (ctypes.c_void_p * n)(*[out[k].data_ptr() for k in range(n)])
+        scratch, stride = self._group_sets(state, n, m)
+        focals, shifts, sets, frames, _ = _group_args(cameras, scratch, stride, out)
+        nf, ns, nsets = _group_args(next_cameras, scratch, stride)[:3]
         turns, nturns = (ctypes.c_int * n)(), (ctypes.c_int * m)()
         fixed = (_ptr(state['packed'], torch.uint8), _i(state['N']), _d(state['cloud_focal']), _i(state['W']), _i(state['H']), _d(float(baseline)), _i(n),
                  focals, shifts, sets, frames, turns)

@@ -1012,6 +1012,33 @@ int kbe_frame_scratch_init_sets(void* scratch, size_t stride, int n, int W, int 
 }  // extern "C"
 
 namespace {
+// the frame sizes the routes take (include/kbe.h): pixel offsets in 32 bits, coordinates through 24-bit multiplies
+bool frame_size_ok(int W, int H) { return W > 0 && H > 0 && (size_t) W * H <= (1u << 30) && W < (1 << 24) && H < (1 << 24); }
+
+// the scratch sets of a group of `n` frames (and their frames and turns, where given): non-null, 16-byte aligned, turns >= 0, no set
+// used twice.  KBE_OK, or KBE_E_INVALID with `bad` or `twice` as the error.
+int check_sets(int n, void* const* sets, uint8_t* const* frames, const int* turns, const char* bad, const char* twice)
+{
+    for (int k = 0; k < n; k++) {
+        KBE_REQUIRE(sets[k] && (!frames || frames[k]) && ((uintptr_t) sets[k] & 15) == 0 && (!turns || turns[k] >= 0), bad);
+        for (int j = 0; j < k; j++) KBE_REQUIRE(sets[j] != sets[k], twice);
+    }
+    return KBE_OK;
+}
+
+// include/kbe.h's `fill_rect` {x0, y0, x1, y1} (NULL: the whole frame)
+FillRect fill_rect_of(const int* r, int W, int H) { return r ? FillRect{ r[0], r[1], r[2], r[3] } : FillRect{ 0, 0, W - 1, H - 1 }; }
+
+// launched() with the error named "<label>/<step>"
+int launched_as(const char* label, const char* step)
+{
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return KBE_OK;
+    char what[96];
+    snprintf(what, sizeof(what), "%s/%s", label, step);
+    return fail(KBE_E_LAUNCH, what, e);
+}
+
 // one frame of a group: its camera, its scratch set, where it goes, which of the set's z-buffers it uses (KBE_STAGE_ZBUF_*)
 struct FrameJob {
     double focal;
@@ -1072,12 +1099,58 @@ int render_jobs(const float* points, const float* image, const float* depth, int
         if ((rc = launched("kbe_render_frame/tiles"))) return rc;
     }
     if (stages & KBE_STAGE_FILL) {
-        FillRect rect = { 0, 0, W - 1, H - 1 };
-        if (fill_rect) { rect.x0 = fill_rect[0]; rect.y0 = fill_rect[1]; rect.x1 = fill_rect[2]; rect.y1 = fill_rect[3]; }
-        launch_fill(s, n, targets, W, H, stages, dirs, rect, n_tiles);
+        launch_fill(s, n, targets, W, H, stages, dirs, fill_rect_of(fill_rect, W, H), n_tiles);
         rc = launched("kbe_render_frame/fill");
     }
     return rc;
+}
+
+// frame `frame` of the fused route on the scratch set at `set`: its camera, and which of the set's counters and banks it uses
+FusedTarget fused_target(void* set, int W, int H, double focal, double baseline, const float* shift3, int parity, uint8_t* frame, int turn)
+{
+    return FusedTarget{ make_camera(W, H, focal, baseline, shift3), carve(set, W, H), scratch_place(set, W, H), parity, frame, nullptr, nullptr, nullptr, nullptr, turn };
+}
+
+// The counter resets of the fused route, each caller's own (kbe_render_video zeroes every set's once per call: k_zero_counters).
+// A frame on its own: the caller keeps no frame parity, so the set's hole counters and list totals (and the binning launch's flags
+// behind them) are zeroed in front of the launch.
+int zero_hole_count(const Scratch& sc, hipStream_t s, const char* what)
+{
+    const hipError_t e = hipMemsetAsync(sc.hole_count, 0, HOLE_COUNT_INTS * sizeof(int), s);
+    return e == hipSuccess ? KBE_OK : fail(KBE_E_LAUNCH, what, e);
+}
+// A set's first turn in a sequence that places ahead: the same, and BOTH banks of its per-tile list counters -- a sequence that was
+// abandoned (an error return, a caller that stopped after a launch that placed ahead) leaves the counters of the bank it placed into
+// standing, and placements appended behind stale counts list sub-blocks twice.
+int start_set(const Scratch& sc, hipStream_t s, const char* what)
+{
+    if (int rc = zero_hole_count(sc, s, what)) return rc;
+    const hipError_t e = hipMemsetAsync(sc.tile_count, 0, 2 * align16(4 * (size_t) sc.tiles_x * sc.tiles_y * CNT_STRIDE), s);
+    return e == hipSuccess ? KBE_OK : fail(KBE_E_LAUNCH, what, e);
+}
+
+// the launches of `n` frames of the packed cloud (fused route): the scatter takes all n frames -- and makes the placements of the
+// `n_next` frames of `next` when asked -- the fill KBE_FILL_JOBS at a time.  The counter resets in front are the callers' (they differ);
+// `label` names the errors.
+int render_fused(hipStream_t s, const void* packed, int N, double cloud_focal, int n, const FusedTarget* now, bool placed, int n_next,
+                 const FusedTarget* next, int stages, int build, const FillRect& rect, double near_depth, const char* label)
+{
+    static const FillDirs dirs = make_fill_dirs();
+    if (stages & KBE_STAGE_TILES) {
+        launch_frames_fused(s, n, packed, N, cloud_focal, now, placed, n_next, next, build, near_depth);
+        if (int rc = launched_as(label, "scatter")) return rc;
+    }
+    if (!(stages & KBE_STAGE_FILL)) return KBE_OK;
+    // a frame counts its holes in the counter of its parity (-1: counter 0) and, with a parity, zeroes the other one for its set's next frame
+    FillTarget targets[KBE_FRAME_JOBS];
+    for (int k = 0; k < n; k++) {
+        const FusedTarget& t = now[k];
+        targets[k] = FillTarget{ t.sc, t.sc.hole_count + (t.parity == 1), t.frame_u8, t.render_f32, 0, t.parity >= 0 ? t.sc.hole_count + (t.parity != 1) : nullptr };
+    }
+    const int W = now[0].cam.W, H = now[0].cam.H;
+    for (int k0 = 0; k0 < n; k0 += KBE_FILL_JOBS)
+        launch_fill(s, n - k0 < KBE_FILL_JOBS ? n - k0 : KBE_FILL_JOBS, targets + k0, W, H, stages, dirs, rect, now[0].sc.tiles_x * now[0].sc.tiles_y);
+    return launched_as(label, "fill");
 }
 }  // namespace
 
@@ -1088,8 +1161,7 @@ int kbe_render_frame_stages(const float* points, const float* image, const float
                             float* existing_f32, float* zee_f32, float* zee_pre_f32, int stages, const int* fill_rect,
                             int raster_w, int raster_n, kbe_stream_t stream)
 {
-    KBE_REQUIRE(scratch && frame_u8 && N >= 0 && N <= (1 << 30) && W > 0 && H > 0 && (size_t) W * H <= (1u << 30) &&
-                W < (1 << 24) && H < (1 << 24) && ((uintptr_t) scratch & 15) == 0, "kbe_render_frame: bad arguments");
+    KBE_REQUIRE(scratch && frame_u8 && N >= 0 && N <= (1 << 30) && frame_size_ok(W, H) && ((uintptr_t) scratch & 15) == 0, "kbe_render_frame: bad arguments");
     KBE_REQUIRE(N == 0 || (points && image && depth), "kbe_render_frame: cloud pointers are NULL");
     const FrameJob job = { focal, shift3, scratch, frame_u8, render_f32, existing_f32, zee_f32, zee_pre_f32, stages & (KBE_STAGE_ZBUF_A | KBE_STAGE_ZBUF_B) };
     return render_jobs(points, image, depth, N, W, H, baseline, 1, &job, stages, fill_rect, raster_w, raster_n, (hipStream_t) stream);
@@ -1099,16 +1171,16 @@ int kbe_render_frame_group(const float* points, const float* image, const float*
                            const double* focals, const float* shifts, void* const* scratch, uint8_t* const* frames_u8, const int* zbuf_flags,
                            int stages, const int* fill_rect, int raster_w, int raster_n, kbe_stream_t stream)
 {
-    KBE_REQUIRE(n_frames >= 1 && n_frames <= KBE_SCATTER_JOBS && focals && shifts && scratch && frames_u8 && N >= 0 && N <= (1 << 30) && W > 0 && H > 0 &&
-                (size_t) W * H <= (1u << 30) && W < (1 << 24) && H < (1 << 24), "kbe_render_frame_group: bad arguments");
+    KBE_REQUIRE(n_frames >= 1 && n_frames <= KBE_SCATTER_JOBS && focals && shifts && scratch && frames_u8 && N >= 0 && N <= (1 << 30) && frame_size_ok(W, H),
+                "kbe_render_frame_group: bad arguments");
     KBE_REQUIRE(N == 0 || (points && image && depth), "kbe_render_frame_group: cloud pointers are NULL");
+    if (int rc = check_sets(n_frames, scratch, frames_u8, nullptr, "kbe_render_frame_group: bad scratch / frame pointer",
+                            "kbe_render_frame_group: the frames of a group need scratch sets of their own"))
+        return rc;
     FrameJob jobs[KBE_SCATTER_JOBS];
-    for (int k = 0; k < n_frames; k++) {
-        KBE_REQUIRE(scratch[k] && frames_u8[k] && ((uintptr_t) scratch[k] & 15) == 0, "kbe_render_frame_group: bad scratch / frame pointer");
-        for (int j = 0; j < k; j++) KBE_REQUIRE(scratch[j] != scratch[k], "kbe_render_frame_group: the frames of a group need scratch sets of their own");
+    for (int k = 0; k < n_frames; k++)
         jobs[k] = FrameJob{ focals[k], shifts + 3 * (size_t) k, scratch[k], frames_u8[k], nullptr, nullptr, nullptr, nullptr,
                             zbuf_flags ? zbuf_flags[k] & (KBE_STAGE_ZBUF_A | KBE_STAGE_ZBUF_B) : 0 };
-    }
     return render_jobs(points, image, depth, N, W, H, baseline, n_frames, jobs, stages & ~(KBE_STAGE_ZBUF_A | KBE_STAGE_ZBUF_B), fill_rect, raster_w, raster_n,
                        (hipStream_t) stream);
 }
@@ -1126,76 +1198,39 @@ int kbe_render_frame_fused(const void* packed, int N, double cloud_focal, int W,
                            const float* shift3, void* scratch, uint8_t* frame_u8, float* render_f32, float* existing_f32,
                            float* zee_f32, float* zee_pre_f32, int stages, const int* fill_rect, int parity, kbe_stream_t stream)
 {
-    KBE_REQUIRE(packed && scratch && frame_u8 && N >= 0 && N <= KBE_FUSED_MAX_POINTS && W > 0 && H > 0 && (size_t) W * H <= (1u << 30) &&
-                W < (1 << 24) && H < (1 << 24) && ((uintptr_t) scratch & 15) == 0 && cloud_focal > 0.0 && parity >= -1 && parity <= 1,
-                "kbe_render_frame_fused: bad arguments");
-    static const FillDirs dirs = make_fill_dirs();
+    KBE_REQUIRE(packed && scratch && frame_u8 && N >= 0 && N <= KBE_FUSED_MAX_POINTS && frame_size_ok(W, H) && ((uintptr_t) scratch & 15) == 0 &&
+                cloud_focal > 0.0 && parity >= -1 && parity <= 1, "kbe_render_frame_fused: bad arguments");
     const hipStream_t s = (hipStream_t) stream;
-    const Scratch sc = carve(scratch, W, H);
-    const Camera cam = make_camera(W, H, focal, baseline, shift3);
-    const int n_tiles = sc.tiles_x * sc.tiles_y;
-    int* const count_now = sc.hole_count + (parity == 1 ? 1 : 0);
-    int* const count_next = sc.hole_count + (parity == 1 ? 0 : 1);
-    int rc = KBE_OK;
-    if (parity < 0 && !(stages & KBE_STAGE_KEEP_HOLE_COUNT)) {
-        // a frame on its own: the caller keeps no frame parity, so the hole counters (and the binning launch's flags behind
-        // them) are zeroed in front of the launch
-        const hipError_t e = hipMemsetAsync(sc.hole_count, 0, HOLE_COUNT_INTS * sizeof(int), s);
-        if (e != hipSuccess) return fail(KBE_E_LAUNCH, "kbe_render_frame_fused: hipMemsetAsync", e);
-    }
-    if (stages & KBE_STAGE_TILES) {
-        const FusedTarget t = { cam, sc, scratch_place(scratch, W, H), parity, frame_u8, render_f32, existing_f32, zee_f32, zee_pre_f32, -1 };
-        launch_frames_fused(s, 1, packed, N, cloud_focal, &t, false, 0, nullptr, fused_build_of_stages(stages));
-        if ((rc = launched("kbe_render_frame_fused/scatter"))) return rc;
-    }
-    if (stages & KBE_STAGE_FILL) {
-        FillRect rect = { 0, 0, W - 1, H - 1 };
-        if (fill_rect) { rect.x0 = fill_rect[0]; rect.y0 = fill_rect[1]; rect.x1 = fill_rect[2]; rect.y1 = fill_rect[3]; }
-        const FillTarget target = { sc, count_now, frame_u8, render_f32, 0, parity >= 0 ? count_next : nullptr };
-        launch_fill(s, 1, &target, W, H, stages, dirs, rect, n_tiles);
-        rc = launched("kbe_render_frame_fused/fill");
-    }
-    return rc;
+    FusedTarget t = fused_target(scratch, W, H, focal, baseline, shift3, parity, frame_u8, -1);
+    t.render_f32 = render_f32; t.existing_f32 = existing_f32; t.zee_f32 = zee_f32; t.zee_pre_f32 = zee_pre_f32;
+    if (parity < 0 && !(stages & KBE_STAGE_KEEP_HOLE_COUNT))
+        if (int rc = zero_hole_count(t.sc, s, "kbe_render_frame_fused: hipMemsetAsync")) return rc;
+    return render_fused(s, packed, N, cloud_focal, 1, &t, false, 0, nullptr, stages, fused_build_of_stages(stages), fill_rect_of(fill_rect, W, H), 0.0,
+                        "kbe_render_frame_fused");
 }
-
 
 int kbe_render_frame_group_fused(const void* packed, int N, double cloud_focal, int W, int H, double baseline, int n_frames, const double* focals,
                                  const float* shifts, void* const* scratch, uint8_t* const* frames_u8, const int* parities, int stages,
                                  const int* fill_rect, kbe_stream_t stream)
 {
-    KBE_REQUIRE(packed && n_frames >= 1 && n_frames <= KBE_FRAME_JOBS && focals && shifts && scratch && frames_u8 && N >= 0 && N <= KBE_FUSED_MAX_POINTS && W > 0 && H > 0 &&
-                (size_t) W * H <= (1u << 30) && W < (1 << 24) && H < (1 << 24) && cloud_focal > 0.0, "kbe_render_frame_group_fused: bad arguments");
-    static const FillDirs dirs = make_fill_dirs();
+    KBE_REQUIRE(packed && n_frames >= 1 && n_frames <= KBE_FRAME_JOBS && focals && shifts && scratch && frames_u8 && N >= 0 && N <= KBE_FUSED_MAX_POINTS &&
+                frame_size_ok(W, H) && cloud_focal > 0.0, "kbe_render_frame_group_fused: bad arguments");
+    if (int rc = check_sets(n_frames, scratch, frames_u8, nullptr, "kbe_render_frame_group_fused: bad scratch / frame pointer",
+                            "kbe_render_frame_group_fused: the frames of a group need scratch sets of their own"))
+        return rc;
     const hipStream_t s = (hipStream_t) stream;
     FusedTarget ft[KBE_FRAME_JOBS];
-    FillTarget targets[KBE_FRAME_JOBS];
-    int n_tiles = 0, rc = KBE_OK;
     for (int k = 0; k < n_frames; k++) {
-        KBE_REQUIRE(scratch[k] && frames_u8[k] && ((uintptr_t) scratch[k] & 15) == 0, "kbe_render_frame_group_fused: bad scratch / frame pointer");
-        for (int j = 0; j < k; j++) KBE_REQUIRE(scratch[j] != scratch[k], "kbe_render_frame_group_fused: the frames of a group need scratch sets of their own");
         const int par = parities ? parities[k] : -1;
         KBE_REQUIRE(par >= -1 && par <= 1, "kbe_render_frame_group_fused: parity is -1, 0 or 1");
-        const Scratch sc = carve(scratch[k], W, H);
-        n_tiles = sc.tiles_x * sc.tiles_y;
-        if (par < 0 && !(stages & KBE_STAGE_KEEP_HOLE_COUNT)) {
-            const hipError_t e = hipMemsetAsync(sc.hole_count, 0, HOLE_COUNT_INTS * sizeof(int), s);
-            if (e != hipSuccess) return fail(KBE_E_LAUNCH, "kbe_render_frame_group_fused: hipMemsetAsync", e);
-        }
-        ft[k] = FusedTarget{ make_camera(W, H, focals[k], baseline, shifts + 3 * (size_t) k), sc, scratch_place(scratch[k], W, H), par, frames_u8[k], nullptr, nullptr, nullptr, nullptr, -1 };
-        targets[k] = FillTarget{ sc, sc.hole_count + (par == 1 ? 1 : 0), frames_u8[k], nullptr, 0, par >= 0 ? sc.hole_count + (par == 1 ? 0 : 1) : nullptr };
+        ft[k] = fused_target(scratch[k], W, H, focals[k], baseline, shifts + 3 * (size_t) k, par, frames_u8[k], -1);
     }
-    if (stages & KBE_STAGE_TILES) {
-        launch_frames_fused(s, n_frames, packed, N, cloud_focal, ft, false, 0, nullptr, fused_build_of_stages(stages));
-        if ((rc = launched("kbe_render_frame_group_fused/scatter"))) return rc;
-    }
-    if (stages & KBE_STAGE_FILL) {
-        FillRect rect = { 0, 0, W - 1, H - 1 };
-        if (fill_rect) { rect.x0 = fill_rect[0]; rect.y0 = fill_rect[1]; rect.x1 = fill_rect[2]; rect.y1 = fill_rect[3]; }
-        for (int k0 = 0; k0 < n_frames; k0 += KBE_FILL_JOBS)       // the fill takes KBE_FILL_JOBS frames per launch
-            launch_fill(s, n_frames - k0 < KBE_FILL_JOBS ? n_frames - k0 : KBE_FILL_JOBS, targets + k0, W, H, stages, dirs, rect, n_tiles);
-        rc = launched("kbe_render_frame_group_fused/fill");
-    }
-    return rc;
+    // (every argument has been checked: only now is anything enqueued)
+    for (int k = 0; k < n_frames; k++)
+        if (ft[k].parity < 0 && !(stages & KBE_STAGE_KEEP_HOLE_COUNT))
+            if (int rc = zero_hole_count(ft[k].sc, s, "kbe_render_frame_group_fused: hipMemsetAsync")) return rc;
+    return render_fused(s, packed, N, cloud_focal, n_frames, ft, false, 0, nullptr, stages, fused_build_of_stages(stages), fill_rect_of(fill_rect, W, H), 0.0,
+                        "kbe_render_frame_group_fused");
 }
 
 int kbe_render_frame_group_ahead_ok(int N, int W, int H, int n_frames, int n_next)
@@ -1209,73 +1244,40 @@ int kbe_render_frame_group_ahead(const void* packed, int N, double cloud_focal, 
                                  const double* next_focals, const float* next_shifts, void* const* next_scratch, const int* next_turns, int stages,
                                  const int* fill_rect, double near_depth, kbe_stream_t stream)
 {
-    KBE_REQUIRE(packed && n_frames >= 1 && n_frames <= KBE_FRAME_JOBS && focals && shifts && scratch && frames_u8 && turns && N >= 0 && N <= KBE_FUSED_MAX_POINTS && W > 0 && H > 0 &&
-                (size_t) W * H <= (1u << 30) && W < (1 << 24) && H < (1 << 24) && cloud_focal > 0.0, "kbe_render_frame_group_ahead: bad arguments");
+    KBE_REQUIRE(packed && n_frames >= 1 && n_frames <= KBE_FRAME_JOBS && focals && shifts && scratch && frames_u8 && turns && N >= 0 && N <= KBE_FUSED_MAX_POINTS &&
+                frame_size_ok(W, H) && cloud_focal > 0.0, "kbe_render_frame_group_ahead: bad arguments");
     KBE_REQUIRE(n_next >= 0 && n_next <= KBE_FRAME_JOBS && (n_next == 0 || (next_focals && next_shifts && next_scratch && next_turns)), "kbe_render_frame_group_ahead: bad next group");
     KBE_REQUIRE(near_depth >= 0.0 && near_depth < 1.0e30, "kbe_render_frame_group_ahead: near_depth is a depth (0: unknown)");
     KBE_REQUIRE(n_next == 0 || fused_can_place_ahead(N, W, H, n_frames, n_next), "kbe_render_frame_group_ahead: too many placements for the tile launch (kbe_render_frame_group_ahead_ok)");
-    static const FillDirs dirs = make_fill_dirs();
-    const hipStream_t s = (hipStream_t) stream;
-    FusedTarget ft[KBE_FRAME_JOBS], nt[KBE_FRAME_JOBS];
-    FillTarget targets[KBE_FRAME_JOBS];
-    int n_tiles = 0, rc = KBE_OK;
-    for (int k = 0; k < n_frames; k++) {
-        KBE_REQUIRE(scratch[k] && frames_u8[k] && ((uintptr_t) scratch[k] & 15) == 0 && turns[k] >= 0, "kbe_render_frame_group_ahead: bad scratch / frame pointer / turn");
-        for (int j = 0; j < k; j++) KBE_REQUIRE(scratch[j] != scratch[k], "kbe_render_frame_group_ahead: the frames of a group need scratch sets of their own");
-        const Scratch sc = carve(scratch[k], W, H);
-        n_tiles = sc.tiles_x * sc.tiles_y;
-        const int par = turns[k] & 1;
-        ft[k] = FusedTarget{ make_camera(W, H, focals[k], baseline, shifts + 3 * (size_t) k), sc, scratch_place(scratch[k], W, H), par, frames_u8[k], nullptr, nullptr, nullptr, nullptr, turns[k] };
-        targets[k] = FillTarget{ sc, sc.hole_count + par, frames_u8[k], nullptr, 0, sc.hole_count + (par ^ 1) };
-    }
-    for (int k = 0; k < n_next; k++) {
-        KBE_REQUIRE(next_scratch[k] && ((uintptr_t) next_scratch[k] & 15) == 0 && next_turns[k] >= 0, "kbe_render_frame_group_ahead: bad scratch / turn of the next group");
-        for (int j = 0; j < k; j++) KBE_REQUIRE(next_scratch[j] != next_scratch[k], "kbe_render_frame_group_ahead: the frames of a group need scratch sets of their own");
+    const char* const twice = "kbe_render_frame_group_ahead: the frames of a group need scratch sets of their own";
+    if (int rc = check_sets(n_frames, scratch, frames_u8, turns, "kbe_render_frame_group_ahead: bad scratch / frame pointer / turn", twice)) return rc;
+    if (int rc = check_sets(n_next, next_scratch, nullptr, next_turns, "kbe_render_frame_group_ahead: bad scratch / turn of the next group", twice)) return rc;
+    for (int k = 0; k < n_next; k++)
         for (int j = 0; j < n_frames; j++)
             KBE_REQUIRE(next_scratch[k] != scratch[j] || next_turns[k] == turns[j] + 1, "kbe_render_frame_group_ahead: a set used by both groups takes consecutive turns");
-        nt[k] = FusedTarget{ make_camera(W, H, next_focals[k], baseline, next_shifts + 3 * (size_t) k), carve(next_scratch[k], W, H), scratch_place(next_scratch[k], W, H),
-                             next_turns[k] & 1, nullptr, nullptr, nullptr, nullptr, nullptr, next_turns[k] };
-    }
-    // (every argument has been checked: only now is anything enqueued)
-    // A set's first turn -- in this group, without placements made ahead, or joining the sequence with the next group: its hole
-    // counters and list totals start from zero (as a frame on its own zeroes them), and so do BOTH banks of its per-tile list
-    // counters: a sequence that was abandoned (an error return, a caller that stopped after a launch that placed ahead) leaves
-    // the counters of the bank it placed into standing, and placements appended behind stale counts list sub-blocks twice.
-    auto start_set = [&](const Scratch& sc) -> hipError_t {
-        hipError_t e = hipMemsetAsync(sc.hole_count, 0, HOLE_COUNT_INTS * sizeof(int), s);
-        if (e == hipSuccess) e = hipMemsetAsync(sc.tile_count, 0, 2 * align16(4 * (size_t) sc.tiles_x * sc.tiles_y * CNT_STRIDE), s);
-        return e;
-    };
-    for (int k = 0; k < n_frames; k++)
-        if (turns[k] == 0 && !placed) {
-            const hipError_t e = start_set(ft[k].sc);
-            if (e != hipSuccess) return fail(KBE_E_LAUNCH, "kbe_render_frame_group_ahead: hipMemsetAsync", e);
-        }
+    const hipStream_t s = (hipStream_t) stream;
+    FusedTarget ft[KBE_FRAME_JOBS], nt[KBE_FRAME_JOBS];
+    for (int k = 0; k < n_frames; k++) ft[k] = fused_target(scratch[k], W, H, focals[k], baseline, shifts + 3 * (size_t) k, turns[k] & 1, frames_u8[k], turns[k]);
     for (int k = 0; k < n_next; k++)
-        if (next_turns[k] == 0) {
-            const hipError_t e = start_set(nt[k].sc);
-            if (e != hipSuccess) return fail(KBE_E_LAUNCH, "kbe_render_frame_group_ahead: hipMemsetAsync", e);
-        }
-    if (stages & KBE_STAGE_TILES) {
-        launch_frames_fused(s, n_frames, packed, N, cloud_focal, ft, placed != 0, n_next, nt, fused_build_of_stages(stages), near_depth);
-        if ((rc = launched("kbe_render_frame_group_ahead/scatter"))) return rc;
-    }
-    if (stages & KBE_STAGE_FILL) {
-        FillRect rect = { 0, 0, W - 1, H - 1 };
-        if (fill_rect) { rect.x0 = fill_rect[0]; rect.y0 = fill_rect[1]; rect.x1 = fill_rect[2]; rect.y1 = fill_rect[3]; }
-        for (int k0 = 0; k0 < n_frames; k0 += KBE_FILL_JOBS)
-            launch_fill(s, n_frames - k0 < KBE_FILL_JOBS ? n_frames - k0 : KBE_FILL_JOBS, targets + k0, W, H, stages, dirs, rect, n_tiles);
-        rc = launched("kbe_render_frame_group_ahead/fill");
-    }
-    return rc;
+        nt[k] = fused_target(next_scratch[k], W, H, next_focals[k], baseline, next_shifts + 3 * (size_t) k, next_turns[k] & 1, nullptr, next_turns[k]);
+    // (every argument has been checked: only now is anything enqueued)
+    // A set's first turn -- in this group, without placements made ahead, or joining the sequence with the next group -- starts from zero
+    for (int k = 0; k < n_frames; k++)
+        if (turns[k] == 0 && !placed)
+            if (int rc = start_set(ft[k].sc, s, "kbe_render_frame_group_ahead: hipMemsetAsync")) return rc;
+    for (int k = 0; k < n_next; k++)
+        if (next_turns[k] == 0)
+            if (int rc = start_set(nt[k].sc, s, "kbe_render_frame_group_ahead: hipMemsetAsync")) return rc;
+    return render_fused(s, packed, N, cloud_focal, n_frames, ft, placed != 0, n_next, nt, stages, fused_build_of_stages(stages), fill_rect_of(fill_rect, W, H),
+                        near_depth, "kbe_render_frame_group_ahead");
 }
 
 int kbe_render_pointcloud_tiled(const float* points, const float* data, int N, int C, int W, int H, double focal,
                                 double baseline, const float* shift3, void* scratch, float* render, float* existing,
                                 kbe_stream_t stream)
 {
-    KBE_REQUIRE(scratch && render && existing && N >= 0 && N <= (1 << 30) && C > 0 && W > 0 && H > 0 && (size_t) W * H <= (1u << 30) &&
-                W < (1 << 24) && H < (1 << 24) && ((uintptr_t) scratch & 15) == 0, "kbe_render_pointcloud_tiled: bad arguments");
+    KBE_REQUIRE(scratch && render && existing && N >= 0 && N <= (1 << 30) && C > 0 && frame_size_ok(W, H) && ((uintptr_t) scratch & 15) == 0,
+                "kbe_render_pointcloud_tiled: bad arguments");
     KBE_REQUIRE(N == 0 || (points && data), "kbe_render_pointcloud_tiled: cloud pointers are NULL");
     const hipStream_t s = (hipStream_t) stream;
     const Scratch sc = carve(scratch, W, H);
@@ -1358,8 +1360,8 @@ int kbe_render_video(const float* points, const float* image, const float* depth
                      double cloud_focal, int flags, kbe_stream_t stream, kbe_stream_t copy_stream, int lanes,
                      const kbe_stream_t* lane_streams, double near_depth)
 {
-    KBE_REQUIRE(n_frames >= 0 && focals && shifts && stage && host_out && W > 0 && H > 0 && batch >= -64 && (!packed || cloud_focal > 0.0) &&
-                (size_t) W * H <= (1u << 30) && W < (1 << 24) && H < (1 << 24), "kbe_render_video: bad arguments");
+    KBE_REQUIRE(n_frames >= 0 && focals && shifts && stage && host_out && frame_size_ok(W, H) && batch >= -64 && (!packed || cloud_focal > 0.0),
+                "kbe_render_video: bad arguments");
     KBE_REQUIRE((crop_w == 0 && crop_h == 0) || (crop_w > 0 && crop_h > 0 && crop_w <= W && crop_h <= H), "kbe_render_video: bad crop");
     KBE_REQUIRE(lanes >= 1 && lanes <= KBE_MAX_LANES && (lanes == 1 || lane_streams), "kbe_render_video: bad lanes");
     KBE_REQUIRE(near_depth >= 0.0 && near_depth < 1.0e30, "kbe_render_video: near_depth is a depth (0: unknown)");
@@ -1458,15 +1460,14 @@ int kbe_render_video(const float* points, const float* image, const float* depth
                                       [&](int n, int n_next) { return fused_can_place_ahead(N, W, H, n, n_next); });
 
     // ---- how a planned launch is enqueued: its frames scattered into scratch sets of their own, filled together, cropped
-    static const FillDirs fill_dirs = make_fill_dirs();
     const int in_flight = plan.single ? lanes : lanes * group;          // frames in flight
     const int fill_flags = in_flight >= KBE_FILL_BY_COUNT_MIN_LANES ? (KBE_STAGE_FILL_BY_COUNT | ((flags & KBE_VIDEO_FILL_DIST) ? KBE_STAGE_FILL_DIST : 0)) : 0;
     const int build = (flags & KBE_VIDEO_FUSED_LEAN) ? 1 : ((flags & KBE_VIDEO_FUSED_ROOMY) ? 2 : 0);
+    const FillRect fill_rect = fill_rect_of(rect, W, H);
     auto dst = [&](const PlanFrame& f) { return (dest == VideoDest::HBM ? host_out : ringed ? ring0 : finished) + (size_t) f.slot * fb; };
-    auto fused_target = [&](const PlanFrame& f, uint8_t* frame) {
-        char* const scr = (char*) scratch + (size_t) f.set * sb;
-        return FusedTarget{ make_camera(W, H, focals[f.frame], baseline, shifts + 3 * (size_t) f.frame), carve(scr, W, H), scratch_place(scr, W, H), f.turn & 1, frame,
-                            nullptr, nullptr, nullptr, nullptr, f.turn };
+    // frame f of the fused route on its scratch set, its parity that of its turn
+    auto fused_target_of = [&](const PlanFrame& f, uint8_t* frame, int turn) {
+        return fused_target((char*) scratch + (size_t) f.set * sb, W, H, focals[f.frame], baseline, shifts + 3 * (size_t) f.frame, f.turn & 1, frame, turn);
     };
     auto render = [&](const PlanLaunch& a) {
         const hipStream_t s = ls[a.lane];
@@ -1486,29 +1487,20 @@ int kbe_render_video(const float* points, const float* image, const float* depth
                                     fr[j].zbuf == PLAN_ZBUF_A ? KBE_STAGE_ZBUF_A : (fr[j].zbuf == PLAN_ZBUF_B ? KBE_STAGE_ZBUF_B : 0) };
             rc = render_jobs(points, image, depth, N, W, H, baseline, a.count, jobs, KBE_VIDEO_STAGES | fill_flags, crop ? rect : nullptr, raster_w, raster_n, s);
         } else if (plan.single) {
-            // the fused scatter on the packed cloud, one frame on its own; a lane's frames alternate between its two hole counters
-            rc = kbe_render_frame_fused(packed, N, cloud_focal, W, H, focals[fr[0].frame], baseline, shifts + 3 * (size_t) fr[0].frame, (char*) scratch + (size_t) fr[0].set * sb,
-                                        raws[0], nullptr, nullptr, nullptr, nullptr, KBE_STAGE_TILES | KBE_STAGE_FILL | fill_flags |
-                                        ((flags & KBE_VIDEO_FUSED_LEAN) ? KBE_STAGE_FUSED_LEAN : 0) | ((flags & KBE_VIDEO_FUSED_ROOMY) ? KBE_STAGE_FUSED_ROOMY : 0),
-                                        crop ? rect : nullptr, fr[0].turn & 1, (kbe_stream_t) s);
+            // the fused scatter on the packed cloud, one frame on its own (turn -1: its placements are made in front of it); a lane's
+            // frames alternate between its two hole counters
+            const FusedTarget t = fused_target_of(fr[0], raws[0], -1);
+            rc = render_fused(s, packed, N, cloud_focal, 1, &t, false, 0, nullptr, KBE_STAGE_TILES | KBE_STAGE_FILL | fill_flags, build, fill_rect, 0.0, "kbe_render_video");
         } else {
             // fused route: the binning launch and the tile launch take all the frames, the fill four at a time; the tile launch also
             // makes the placements of the lane's next launch when the plan says so
             FusedTarget ft[KBE_FRAME_JOBS], nt[KBE_FRAME_JOBS];
-            FillTarget targets[KBE_FRAME_JOBS];
-            for (int j = 0; j < a.count; j++) {
-                ft[j] = fused_target(fr[j], raws[j]);
-                targets[j] = FillTarget{ ft[j].sc, ft[j].sc.hole_count + (fr[j].turn & 1), raws[j], nullptr, 0, ft[j].sc.hole_count + ((fr[j].turn & 1) ^ 1) };
-            }
+            for (int j = 0; j < a.count; j++) ft[j] = fused_target_of(fr[j], raws[j], fr[j].turn);
             const int n_next = a.next >= 0 ? plan.launches[a.next].count : 0;
-            for (int j = 0; j < n_next; j++) nt[j] = fused_target(plan.frames[plan.launches[a.next].first + j], nullptr);
-            launch_frames_fused(s, a.count, packed, N, cloud_focal, ft, a.placed, n_next, nt, build, near_depth);
-            if ((rc = launched("kbe_render_video/scatter"))) return rc;
-            const FillRect fr_rect = { rect[0], rect[1], rect[2], rect[3] };
-            for (int j0 = 0; j0 < a.count; j0 += KBE_FILL_JOBS)
-                launch_fill(s, a.count - j0 < KBE_FILL_JOBS ? a.count - j0 : KBE_FILL_JOBS, targets + j0, W, H, KBE_STAGE_FILL | fill_flags, fill_dirs, fr_rect,
-                            targets[0].sc.tiles_x * targets[0].sc.tiles_y);
-            rc = launched("kbe_render_video/fill");
+            const PlanFrame* const next = n_next ? &plan.frames[plan.launches[a.next].first] : nullptr;
+            for (int j = 0; j < n_next; j++) nt[j] = fused_target_of(next[j], nullptr, next[j].turn);
+            rc = render_fused(s, packed, N, cloud_focal, a.count, ft, a.placed, n_next, nt, KBE_STAGE_TILES | KBE_STAGE_FILL | fill_flags, build, fill_rect, near_depth,
+                              "kbe_render_video");
         }
         for (int j0 = 0; j0 < a.count && rc == KBE_OK && crop; j0 += KBE_FILL_JOBS)
             rc = crop_resize_group(a.count - j0 < KBE_FILL_JOBS ? a.count - j0 : KBE_FILL_JOBS, raws + j0, W, H, crop_w, crop_h, outs + j0, s);

@@ -40,7 +40,7 @@ struct PlanUnit {           // a transfer group, a ring half, a single delivered
     int launch0, launch1;   // its launches: launches[launch0 .. launch1)
 };
 struct VideoPlan {
-    bool single;            // one frame per launch in the one-frame form (kbe_render_frame_fused with parity; bucket: set = lane)
+    bool single;            // one frame per launch in the one-frame form (fused: turn -1, parity turn & 1; bucket: set = lane)
     std::vector<PlanUnit> units;
     std::vector<PlanLaunch> launches;
     std::vector<PlanFrame> frames;

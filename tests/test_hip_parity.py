@@ -630,6 +630,31 @@ def test_pipelined_groups_equal_groups_with_their_placements_in_front(K):
                                    next_cameras=groups[1], next_turn=[1, 2])
 
 
+def test_a_fused_group_with_a_bad_frame_enqueues_nothing(K):
+    """kbe_render_frame_group_fused checks every frame before it enqueues anything: a misaligned scratch set in the second frame is
+    refused, and the first frame's set -- parity -1, whose hole counters the call would zero first -- is left as it was."""
+    import ctypes
+    from ken_burns_effect_amd import common
+    size = (96, 128)
+    settings, oc = _scene(size, 5)
+    cams = common.frame_cameras(settings, oc)[:2]
+    state = common._prepared_cloud(K, oc)
+    K._pack(state)
+    stride = K.scratch_stride(state)
+    scratch = torch.full((2 * stride,), 0xAB, dtype=torch.uint8, device='cuda')
+    out = torch.zeros(2, size[0], size[1], 3, dtype=torch.uint8, device='cuda')
+    focals = (ctypes.c_double * 2)(*[float(c[0]) for c in cams])
+    shifts = (ctypes.c_float * 6)(*[float(v) for c in cams for v in c[1]])
+    sets = (ctypes.c_void_p * 2)(scratch.data_ptr(), scratch.data_ptr() + stride + 8)
+    frames = (ctypes.c_void_p * 2)(out[0].data_ptr(), out[1].data_ptr())
+    rc = K.lib.kbe_render_frame_group_fused(ctypes.c_void_p(state['packed'].data_ptr()), state['N'], ctypes.c_double(state['cloud_focal']), size[1], size[0],
+                                            ctypes.c_double(oc['dblBaseline']), 2, focals, shifts, sets, frames, None, 6, None,
+                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert rc == -1 and b'bad scratch' in K.lib.kbe_last_error()
+    assert bool((scratch == 0xAB).all()), 'the first frame\'s set was written before the second frame was checked'
+
+
 @pytest.mark.parametrize('kind', ['incoherent', 'pile_up', 'tiny', 'empty'])
 def test_pipelined_groups_through_the_slow_paths(K, kind):
     """The one-launch scatter on clouds that leave the normal path: a cloud in random order (every sub-block is wide: the list
