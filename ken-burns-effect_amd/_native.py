@@ -13,6 +13,13 @@ import os
 
 import torch
 
+from . import video_shape
+# (the flag bits under the header's names, and the rules and thresholds of a video call's shape that lived here before video_shape.py did)
+from .video_shape import (DEFAULT_FILL_GROUP, DEFAULT_HOST_LANES, FUSED_DENSE, FUSED_HOST_GROUP, KBE_STAGE_FUSED_LEAN, KBE_STAGE_FUSED_ROOMY,  # noqa: F401
+                          KBE_STAGE_PROJECT, KBE_VIDEO_FILL_DIST, KBE_VIDEO_FILL_GROUP, KBE_VIDEO_GROUP, KBE_VIDEO_FREE_TRANSFERS,
+                          KBE_VIDEO_EVEN_GROUPS, KBE_VIDEO_NO_AHEAD, KBE_VIDEO_FAST_RAMP, KBE_VIDEO_FUSED_LEAN, KBE_VIDEO_FUSED_ROOMY, KBE_VIDEO_SDMA,
+                          KBE_VIDEO_INJECT_FAULT, KBE_VIDEO_INJECT_TIMEOUT, LINK_BYTES_PER_US, Switches, lanes_for_delivery, transfer_group)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('KBE_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libkbe_hip.so')      # (KBE_LIB_PATH: a variant build of the same ABI -- measurements)
 
@@ -34,23 +41,7 @@ FUSED_MAX_DENSITY = 20.0         # clouds up to this many points per pixel take 
                                  # (profiles/r05_density_sweep.txt; the bucket route: 153 / 14 083 us at 4 / 9, the atomic kernels 2.1 / 5.2 / 20.5 ms at 4 / 9 / 24).
                                  # (4.5 in round 4, 1.5 before.)
 FUSED_MAX_POINTS = 1 << 28       # the packed cloud's route addresses points by 32-bit byte offsets (KBE_FUSED_MAX_POINTS, kbe_tiles.h): larger clouds take the bucket route
-FUSED_DENSE = 1.5                # "denser than the raster" from here on: delivered to host memory such a video takes three frames per launch on every lane (two until round 6)
-FUSED_HOST_GROUP = 12  # frames per launch of the fused scatter when the frames are delivered to host memory (KBE_FILL_GROUP overrides): as many as a
-                       # launch's 4 KB of kernel arguments hold.  A launch alone on a stream costs ~5 us besides its frames (ramp and tail: 8 / 12
-                       # frames per launch 16.5 / 16.1 us per frame), and delivered to host memory -- the link binds -- a video runs at the same rate
-                       # with 8 or 12 (17.4-17.6 k frames/s, --steps 75 16.1-16.3 k, --steps 20 13.8-13.9 k either way: tools/batches/gpu_r04_group12.sh)
-DEFAULT_FILL_GROUP = 4 # frames a lane fills per launch when the table-driven fill is on (env KBE_FILL_GROUP, 1..4)
 PROBE_MIN_FRAMES = 128 # delivered videos from this length on have their lanes measured (HipKernels.delivery_lanes); shorter ones take the a-priori estimate
-DEFAULT_HOST_LANES = 2 # of those, the lanes used when the frames are delivered to pinned host memory AND the link binds (host_lanes below)
-
-
-LINK_BYTES_PER_US = 53.0e3     # what the PCIe link moves for this loop (measured: 53-54.5 GB/s of the 63 GB/s Gen5 x16)
-
-
-def lanes_for_delivery(lanes, render_us, frame_bytes):
-    """Two lanes where the link binds (it needs 1.5 x longer per frame than the rendering), all lanes elsewhere."""
-    link_us = frame_bytes / LINK_BYTES_PER_US
-    return min(lanes, DEFAULT_HOST_LANES) if link_us > 1.5 * render_us else lanes
 
 
 _LANE_STREAMS = {}
@@ -83,40 +74,17 @@ def lane_streams_of(device, n):
     return have[:n]
 
 
-def transfer_group(n_frames, lanes, launch_group, fast_ramp=False):
-    """-(frames per transfer group) of a delivered video of n_frames on `lanes` lanes (kbe_render_video's batch < 0; the first groups
-    ramp 1, 2, 4, ...: include/kbe.h).  Two lanes -- the link binds: groups of up to 32 frames (16 -> 32: 17.3 -> 17.5 k frames/s), a quarter of
-    the video between 64 and 128 frames, 16 below.  More lanes -- the rendering binds, not the link (delivery_lanes): a
-    lane then waits for nothing but its own last transfer, and what a video loses is its END -- the lanes' last groups leave one after
-    the other when nothing is left to render, and groups of 32 deal the frames unevenly to four lanes: a transfer group is what ONE
-    scatter launch renders (`launch_group`).  Measured (tools/batches/gpu_r05_dolly_batch.sh, profiles/r05_transfer_groups.txt): bench --dolly,
-    256 frames, k frames/s delivered with groups of up to 32 / 16 / 12 / 8 frames 10.2 / 10.7 / 10.7 / 11.4 (left in HBM: 13.0);
-    configs[4], 64 frames, groups of 32 / 2: 2.2 / 3.0 k."""
-    if lanes > DEFAULT_HOST_LANES:
-        return -max(1, int(launch_group))
-    # (the ramp is never cut below 16: until late in round 5 a short video's cap was n / 4 alone -- "small enough for each lane to have two
-    # groups of full size", a rule from the blit hand-off's days; with the SDMA engine a transfer fewer is worth more: tools/batches/gpu_r05_short_batch.sh,
-    # k frames/s delivered with the old cap / 8 / 16: 16 frames 13.8-13.9 / 14.3 / 14.3, 20 frames 14.8 / 14.9 / 14.9, 30 frames 15.5 / 15.4 / 15.65; 40, 75: equal)
-    return -max(1, min(32, max(n_frames // (2 * lanes), 16, (n_frames + 1) // 2 if fast_ramp else 0)))
+def forced_host_lanes():
+    """KBE_HOST_LANES: the lanes of a delivered video, whatever the estimate or the probe would say (None: unset)."""
+    env = os.environ.get('KBE_HOST_LANES')
+    return int(env) if env else None
 
 
 def host_lanes(lanes, n_points, W, H, frame_bytes):
-    """The a-priori estimate (HipKernels.delivery_lanes measures instead, once per cloud, when the video is long enough).
-    Lanes of the frame loop when the frames go to pinned host memory (env KBE_HOST_LANES overrides).  Where the PCIe
-    link binds, two lanes ping-pong best (one renders its next group while the other's leaves: 59.1 us per 1024^2 frame of
-    the bench against 60.7 with four and 84.8 with three); where the rendering binds every lane helps (measured, 2 -> 4
-    lanes: 512^2 25.5 -> 18.8 us, dolly 260 -> 155, raw cloud 64 -> 61, 2048^2 raw 305 -> 276, 2048^2 from 16.8 M points
-    427 -> 386).  Which it is, from what is known before the first frame: the link needs frame_bytes / 53 GB/s per frame; a
-    frame of an inpainted cloud (more points than pixels: few holes to fill) renders in about 13.5 us per million points
-    + 12 us per megapixel with four lanes, and never in less than the ~14 us its four launches take; a cloud without
-    appended points leaves holes whose fill dominates (rendering binds).  The link binds when it needs 1.5 x longer."""
-    env = os.environ.get('KBE_HOST_LANES')
-    if env:
-        return min(lanes, max(1, int(env)))
-    link_us = frame_bytes / 53.0e3
-    render_us = max(14.0, 13.5e-6 * n_points + 12.0e-6 * W * H)
-    link_bound = n_points > W * H and link_us > 1.5 * render_us
-    return min(lanes, DEFAULT_HOST_LANES) if link_bound else lanes
+    """video_shape.host_lanes, the a-priori estimate of a delivered video's lanes, under env KBE_HOST_LANES."""
+    return video_shape.host_lanes(lanes, n_points, W, H, frame_bytes, forced_host_lanes())
+
+
 _lib = None
 
 
@@ -200,11 +168,13 @@ def _group_args(cameras, scratch, stride, out=None, fill_rect=None):
     return focals, shifts, sets, frames, _rect(fill_rect)
 
 
+_BUILD_BITS = {'lean': (KBE_STAGE_FUSED_LEAN, KBE_VIDEO_FUSED_LEAN), 'roomy': (KBE_STAGE_FUSED_ROOMY, KBE_VIDEO_FUSED_ROOMY)}
+
+
 def fused_build_bits(video=False):
     """KBE_FUSED_CAP=lean|roomy (tests, measurements): the flag that forces one build of the fused route's tile launches
     (KBE_STAGE_FUSED_LEAN / _ROOMY, or the kbe_render_video form).  The environment is read HERE, per call; the library reads none."""
-    cap = os.environ.get('KBE_FUSED_CAP')
-    bits = {'lean': (1024, 2048), 'roomy': (2048, 4096)}.get(cap)
+    bits = _BUILD_BITS.get(os.environ.get('KBE_FUSED_CAP'))
     return bits[1 if video else 0] if bits else 0
 
 
@@ -214,6 +184,37 @@ HANDOFF_DEFAULT = 'sdma'    # measured (profiles/r05_handoff_sdma.txt): 20 frame
 def handoff_by_sdma():
     """Do a delivered video's frame groups leave through an SDMA engine (KBE_VIDEO_SDMA) or through hipMemcpyAsync (a blit kernel)?"""
     return os.environ.get('KBE_HANDOFF', HANDOFF_DEFAULT) == 'sdma'
+
+
+def video_switches():
+    """Every environment switch that shapes a video call (HipKernels.render_video), read once per call -- tests flip them between
+    calls -- into a video_shape.Switches record; video_shape.call_shape decides by the record, nothing else of a call reads them.
+    Defaults in brackets:
+      KBE_FILL_DIST [auto] | 0 | 1         the table-driven hole fill (auto: a cloud without appended points seen by a camera that zooms out)
+      KBE_FILL_GROUP [by route, frame size and destination]   frames per launch of a lane: 1..4 on the bucket route, 1..12 on the fused one
+      KBE_HOST_LANES [estimated or measured]    lanes of a delivered video (forced_host_lanes: host_lanes and delivery_lanes take it too)
+      KBE_DELIVERY_BATCH [0 = transfer_group]   frames per transfer: < 0 groups per lane, > 0 the staged ring
+      KBE_RAMP [classic] | fast            transfer groups of 1, 2, 4, ... or 1, 3, 7, ... frames (KBE_VIDEO_FAST_RAMP)
+      KBE_FREE_TRANSFERS [auto] | 0 | 1    the lanes do not take turns on the link (auto: with the table-driven fill)
+      KBE_EVEN_GROUPS [0] | 1              (dev) transfer groups of one size, no ramp
+      KBE_AHEAD [1] | 0                    0: every group of the fused route keeps its own placement launch (KBE_VIDEO_NO_AHEAD)
+      KBE_FUSED_CAP lean | roomy           forces a build of the tile launches (fused_build_bits, which the one-frame and group entries use too)
+      KBE_HANDOFF [sdma] | blit            how a delivered video's frame groups leave (handoff_by_sdma)
+      KBE_INJECT_HANDOFF_FAULT, KBE_INJECT_HANDOFF_TIMEOUT = 1    test hooks of the SDMA hand-off
+      KBE_SCRATCH_BUDGET_MB [half of the free device memory]      what the loop's scratch sets may take
+    (KBE_SHARE_LISTS is near_depth's; KBE_LANES, KBE_FUSED and KBE_NO_RASTER_HINT are prepare_cloud's.)"""
+    env = os.environ.get
+    batch = env('KBE_DELIVERY_BATCH', '0')
+    try:
+        batch = int(batch)
+    except ValueError:
+        raise KbeError('KBE_DELIVERY_BATCH=%r is not an integer (frames per transfer: < 0 groups per lane, > 0 staged ring)' % batch)
+    fill_dist, fill_group, free, budget = env('KBE_FILL_DIST', 'auto'), env('KBE_FILL_GROUP'), env('KBE_FREE_TRANSFERS', 'auto'), env('KBE_SCRATCH_BUDGET_MB')
+    return Switches(fill_dist=None if fill_dist == 'auto' else fill_dist != '0', fill_group=int(fill_group) if fill_group else None,
+                    host_lanes=forced_host_lanes(), delivery_batch=batch, fast_ramp=env('KBE_RAMP', 'classic') == 'fast',
+                    free_transfers=None if free == 'auto' else free == '1', even_groups=env('KBE_EVEN_GROUPS') == '1', no_ahead=env('KBE_AHEAD') == '0',
+                    build_bits=fused_build_bits(video=True), sdma=handoff_by_sdma(), inject_fault=env('KBE_INJECT_HANDOFF_FAULT') == '1',
+                    inject_timeout=env('KBE_INJECT_HANDOFF_TIMEOUT') == '1', scratch_budget_mb=float(budget) if budget else None)
 
 
 class HipKernels:
@@ -430,7 +431,7 @@ class HipKernels:
                                                         _i(state['W']), _i(state['H']), _d(float(focal)), _d(float(baseline)),
                                                         _shift(shift3), _ptr(state['scratch'], torch.uint8), _ptr(frame, torch.uint8),
                                                         _ptr(render_f32), _ptr(existing_f32), _ptr(zee_f32), _ptr(zee_pre_f32),
-                                                        _i((int(stages) & ~1) | fused_build_bits()), rect, _i(int(parity)), _stream()), 'kbe_render_frame_fused')
+                                                        _i((int(stages) & ~KBE_STAGE_PROJECT) | fused_build_bits()), rect, _i(int(parity)), _stream()), 'kbe_render_frame_fused')
             return frame
         self._check(self.lib.kbe_render_frame_stages(_ptr(state['points']), _ptr(state['image']), _ptr(state['depth']),
                                                      _i(state['N']), _i(state['W']), _i(state['H']), _d(float(focal)),
@@ -532,13 +533,12 @@ class HipKernels:
             state['scratch_stride'] = int(self.lib.kbe_video_scratch_stride(_i(state['W']), _i(state['H']), _i(state['N'])))
         return state['scratch_stride']
 
-    def scratch_set_budget(self, state):
-        """How many scratch sets (kbe_video_scratch_stride bytes each) a video loop may hold: KBE_SCRATCH_BUDGET_MB, or half of the
-        device memory that is free now plus what the cloud's sets already hold; at least one per lane."""
+    def scratch_set_budget(self, state, budget_mb=None):
+        """How many scratch sets (kbe_video_scratch_stride bytes each) a video loop may hold: `budget_mb` (KBE_SCRATCH_BUDGET_MB), or half
+        of the device memory that is free now plus what the cloud's sets already hold; at least one per lane."""
         stride = self.scratch_stride(state)
-        env = os.environ.get('KBE_SCRATCH_BUDGET_MB')
-        if env:
-            budget = float(env) * 1e6
+        if budget_mb is not None:
+            budget = budget_mb * 1e6
         else:
             free, _ = torch.cuda.mem_get_info(state['points'].device)
             held = state['scratch_groups'].numel() if 'scratch_groups' in state else 0
@@ -546,77 +546,33 @@ class HipKernels:
         return max(state['lanes'], int(budget // stride))
 
     def video_launch_shape(self, state, cameras, batch, to_host=False, max_group=None):
-        """(flags of kbe_render_video, frames per launch, fused route?) for a video of `cameras`.
-        KBE_VIDEO_FILL_DIST, the table-driven hole fill: for videos whose frames have hundreds of thousands of holes -- a
-        cloud without appended points (no inpainting) seen by a camera that zooms out (a dolly zoom lowers the focal length:
-        the image shrinks into an empty border).  Measured, us per frame without / with: dolly 300 / 129 at 1024^2, 77 / 63
-        at 512^2 -- but a raw cloud on the ordinary camera path 35.2 / 37.8, 2048^2 139 / 151 (two more launches per frame
-        that find few holes).  KBE_FILL_DIST=1 / 0 forces it on / off.
-        KBE_VIDEO_FILL_GROUP(n): a lane renders n frames into n scratch sets, every launch taking all n.  A launch on its
-        own is bound by its ramp and its tail as much as by its work (the fused scatter of a 1024^2 frame: 35 us alone, 27 /
-        23 per frame with 2 / 4 frames per launch), so frames left in HBM take 27.5 / 25.3 / 26.7 us with n = 1 / 2 / 4 on
-        four lanes (the lanes fill the same gaps), and where the PCIe link binds (frames delivered to host memory: 59 us
-        per frame whatever n) n = 4 leaves the most of the chip idle.  Small frames are bound by their launches: 4 up to
-        576^2.  KBE_FILL_GROUP overrides.
-        The route: the state's (prepare_cloud)."""
-        W, H = state['W'], state['H']
-        mode = os.environ.get('KBE_FILL_DIST', 'auto')
-        zooms_out = len(cameras) > 0 and min(float(c[0]) for c in cameras) < 0.9 * state['cloud_focal']
-        flags = int(state['N'] <= W * H and zooms_out) if mode == 'auto' else int(mode != '0')
-        # (until round 5 a zoom-out took the bucket route: the density of the points on the shrinking image grows along the video, the fused
-        # route's candidate lists of 512 sub-blocks overflowed and it lost 147 : 97 us per frame.  With lists of 2048 it wins: 82 against
-        # 90 us per 1024^2 dolly frame left in HBM, 21.8 against 23.5 at 512^2 -- profiles/r05_dolly_routes.txt.  KBE_FUSED=0 still forces the other.)
-        fused = bool(state.get('fused'))
-        if os.environ.get('KBE_FILL_GROUP'):
-            group = max(1, min(12 if fused else 4, int(os.environ['KBE_FILL_GROUP'])))
-        elif flags:
-            # the table-driven fill: launches bound by their own chains of look-ups -- four frames per fill launch; the fused scatter in
-            # front of them takes eight (measured, us per dolly frame left in HBM / k frames/s delivered with 4 / 8 / 12: 82.1 / 80.4 / 79.7, 9.6 / 9.9 / 9.8)
-            group = 8 if fused else DEFAULT_FILL_GROUP
-        elif fused:
-            # eight where the link binds (the rendering then only has to stay out of the transfers' way: the fewer, larger
-            # launches the better), four for frames left in HBM on four lanes -- since a group's tile launch also makes the next
-            # group's placements (one scatter launch per group) four frames per launch are as good as or better than two at every
-            # size (measured, us per frame left in HBM with 2 / 4 / 8 frames per launch: 640^2 12.2 / 11.3 / 11.4, 896^2 20.3 / 20.9 / 21.3,
-            # 1024^2 25.5 / 24.9 / 25.0, 1280^2 41.4 / 40.5 / 41.2, 1536^2 59.3 / 58.4 / 58.5; with a placement launch per group, round
-            # 3's first half: 1024^2 25.3 / 26.7; the bucket route: 13.7, 18.8, 25.5, 29.4, 51.7, 72.8)
-            group = FUSED_HOST_GROUP if to_host else 4
-            if state['N'] > FUSED_DENSE * W * H:              # (left in HBM too since round 6: four per launch was the slowest of 2 / 3 / 4 there)
-                # a cloud much denser than the raster is bound by its rendering, not by the link: few frames per launch on every lane.  Round 4
-                # (blit hand-off: long launches next to another lane's copy kernel slowed each other), 16.8 M points at 2048^2, us per
-                # delivered frame with 8 / 4 / 2 frames per launch on four lanes: 446 / 422 / 395.  Round 6, SDMA hand-off, frames/s delivered /
-                # left in HBM with 2 / 3 / 4 / 6 / 8: 2 948 / 3 234, 2 941 / 3 246, 2 707 / 3 141, 2 598 / 2 999, 2 390 / 2 974 -- and the launch
-                # alone on a stream 289.5 / 273.8 / 269.1 / 265.6 / 263.7 us per frame (its tail amortised): three is as fast as two for the
-                # video and 5 % faster per launch (tools/batches/gpu_r06_config4_groups.sh, profiles/r06_config4_groups.txt)
-                group = 3
-        else:
-            # the bucket route (measured, us per frame with 1 / 2 / 4 frames per launch: 256^2 13.3 / 9.8 / 6.2, 512^2 13.7 / 9.8 /
-            # 8.6, 640^2 15.1 / 12.8 / 13.1, 768^2 19.1 / 16.4 / 17.4, 896^2 24.8 / 23.8 / 24.3, 1024^2 28.9 / 30.6 / 30.9)
-            group = 4 if W * H <= 576 * 576 else (2 if W * H <= 900 * 900 else 1)
-        if not (batch is None or batch <= 0):
-            group = 1
-        if not fused:
-            group = min(group, 4)
+        """(flags of kbe_render_video, frames per launch, fused route?) for a video of `cameras`, under the environment's switches: the
+        group-and-fill rule of video_shape (fills_with_tables, frames_per_launch -- the measurements are there), of which
+        video_shape.call_shape makes a whole call.  `flags` holds KBE_VIDEO_FILL_DIST and the group field only."""
+        sw = video_switches()
+        N, W, H, fused = state['N'], state['W'], state['H'], bool(state.get('fused'))
+        fill_dist = video_shape.fills_with_tables(N, W, H, HipKernels.zooms_out(state, cameras), sw)
+        group = video_shape.frames_per_launch(N, W, H, fused, fill_dist, batch, to_host, sw)
         if max_group is not None:
             group = max(1, min(group, int(max_group)))
-        return flags | (((group - 1) << 1) if group <= 4 else ((group - 1) << 5)), group, fused
+        return video_shape.launch_flags(fill_dist, group), group, fused
 
     @staticmethod
     def zooms_out(state, cameras):
         return bool(cameras) and min(float(c[0]) for c in cameras) < 0.9 * state['cloud_focal']
 
-    def delivery_lanes(self, state, cameras, baseline, crop=None):
+    def delivery_lanes(self, state, cameras, baseline, crop=None, switches=None):
         """Lanes of the frame loop when the frames go to pinned host memory: two where the link binds, all where the rendering
         does (`host_lanes` has the measurements).  Which it is depends on the cloud, the camera path and the route, so it is
         MEASURED once per cloud, camera-path kind and crop -- twelve of the video's frames rendered into HBM on all lanes, timed
         with two events (a few hundred microseconds, and ONE host synchronisation: the first render_video of a cloud is not
         enqueue-only) -- and kept in the cloud's state; videos shorter than PROBE_MIN_FRAMES (the product's 75 frames: the probe would
         be a third of their work), and the first lookup without a camera path, take the a-priori estimate.  A rank that received the cloud by broadcast takes what rank 0 measured (`delivery_lanes_hint`:
-        sharding.measure_delivery_lanes) and never probes.  Env KBE_HOST_LANES overrides."""
+        sharding.measure_delivery_lanes) and never probes.  Env KBE_HOST_LANES overrides (`switches`: render_video's record, which has read it already)."""
         lanes, W, H = state['lanes'], state['W'], state['H']
-        env = os.environ.get('KBE_HOST_LANES')
-        if env:
-            return min(lanes, max(1, int(env)))
+        forced = forced_host_lanes() if switches is None else switches.host_lanes
+        if forced is not None:
+            return min(lanes, max(1, forced))
         zoom = self.zooms_out(state, cameras)                  # a zoom-out renders differently: its own entry
         hint = state.get('delivery_lanes_hint', {})
         if zoom in hint:                                       # measured on rank 0, broadcast with the cloud (sharding.py)
@@ -628,7 +584,7 @@ class HipKernels:
         # (a video shorter than PROBE_MIN_FRAMES takes the a-priori estimate: the probe renders 24 frames and synchronises the host --
         # 0.5 ms of the 1.4 ms a 64-frame 512^2 video takes, paid by every Pipeline call, each with a cloud of its own: ADVICE r3)
         if len(cameras) < PROBE_MIN_FRAMES or lanes == 1:
-            return host_lanes(lanes, state['N'], W, H, 3 * W * H)
+            return video_shape.host_lanes(lanes, state['N'], W, H, 3 * W * H)
         probe = cameras[::max(1, len(cameras) // 12)][:12]
         out = torch.empty(len(probe), H, W, 3, dtype=torch.uint8, device=state['points'].device)
         self.render_video(state, probe, baseline, crop=crop, host_out=out)                          # warm-up: scratch, streams, the packed cloud
@@ -678,31 +634,15 @@ class HipKernels:
             if not host_out.is_cuda and not host_out.is_pinned():
                 raise KbeError('render_video: host_out must be pinned host memory (or a device tensor)')
             return self._render_video_generic(state, cameras, baseline, crop, host_out)
-        lanes = state['lanes']
-        if host_out.is_cuda:
-            batch, overlap = 0, False
-        else:
-            if not host_out.is_pinned():
-                raise KbeError('render_video: host_out must be pinned host memory (or a device tensor)')
-            # The hand-off (include/kbe.h): < 0 = groups of -batch frames per lane, one hipMemcpyAsync each, the lanes
-            # taking turns on the link (default); 0 = per frame by a copy kernel; > 0 = round 1's staged ring.
-            lanes = self.delivery_lanes(state, cameras, baseline, crop)
-            if batch is None:
-                env = os.environ.get('KBE_DELIVERY_BATCH', '0')
-                try:
-                    batch = int(env)
-                except ValueError:
-                    raise KbeError('KBE_DELIVERY_BATCH=%r is not an integer (frames per transfer: < 0 groups per lane, > 0 staged ring)' % env)
-                # how many frames a transfer group may hold: transfer_group (the first groups ramp 1, 2, 4, 8, 16: include/kbe.h)
-                # (KBE_RAMP=fast: groups of 1, 3, 7, 15, 31, ... frames, capped at half the video -- two transfers fewer than 1, 2, 4, 8, ...
-                # for a 20- or a 75-frame video.  Measured, round 4 (profiles/r04_short_videos.txt): no gain -- 20 frames 14.05 against
-                # 13.93 k frames/s, 75 frames 16.05 against 16.21 k: the larger groups render next to the other lane's transfer, whose
-                # blit kernel's PCIe-bound stores slow them.  Not the default.)
-                fast_ramp = os.environ.get('KBE_RAMP', 'classic') == 'fast'
-                batch = batch or transfer_group(n, lanes, self.video_launch_shape(state, cameras, -1, to_host=True)[1] if lanes > DEFAULT_HOST_LANES else 0, fast_ramp)
-        # the staging buffers grow with |batch| (lanes * (4 + G) frames): never more frames per transfer than the video has, or than 64
-        batch = int(batch)
-        batch = -min(-batch, max(n, 1), 64) if batch < 0 else min(batch, max(n, 1), 64)
+        to_host = not host_out.is_cuda
+        if to_host and not host_out.is_pinned():
+            raise KbeError('render_video: host_out must be pinned host memory (or a device tensor)')
+        sw = video_switches()
+        lanes = self.delivery_lanes(state, cameras, baseline, crop, sw) if to_host else state['lanes']
+        held = state['scratch_groups'].numel() // self.scratch_stride(state) if 'scratch_groups' in state else 0
+        shape = video_shape.call_shape(state['N'], W, H, bool(state.get('fused')), n, self.zooms_out(state, cameras), to_host, batch, lanes, sw,
+                                       held, lambda: self.scratch_set_budget(state, sw.scratch_budget_mb))
+        batch, fused = shape.batch, shape.fused
         need = int(self.lib.kbe_video_stage_bytes(_i(W), _i(H), _i(lanes), _i(batch)))
         if 'stage' not in state or state['stage'].numel() < need:
             state['stage'] = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -713,54 +653,18 @@ class HipKernels:
         focals = (ctypes.c_double * max(n, 1))(*[float(c[0]) for c in cameras])
         shifts = (ctypes.c_float * max(3 * n, 1))(*[float(v) for c in cameras for v in c[1]])
         cw, ch = (0, 0) if crop is None else (int(crop[0]), int(crop[1]))
-        copy_stream = ctypes.c_void_p(state['copy_stream'].cuda_stream) if overlap else _stream()
-        flags, group, fused = self.video_launch_shape(state, cameras, batch, to_host=not host_out.is_cuda)
-        base_flags = flags
+        copy_stream = ctypes.c_void_p(state['copy_stream'].cuda_stream) if overlap and to_host else _stream()
         if fused:
             self._pack(state)
-        # KBE_VIDEO_FREE_TRANSFERS: videos that fill with the tables are bound by their rendering (the link is half idle), and
-        # a lane waiting for its turn on the link only idles: bench --dolly 8.1 k frames/s delivered with turns, 9.1 k without
-        # (512^2 and 2048^2 frames, whose transfers fill the link to 70 %, keep the turns: 57 vs 53 k, 2.65 vs 2.03 k)
-        free = os.environ.get('KBE_FREE_TRANSFERS', 'auto')
-        if not host_out.is_cuda and (free == '1' or (free == 'auto' and flags & 1)):
-            flags |= 8
-        if os.environ.get('KBE_EVEN_GROUPS') == '1':        # (dev) transfer groups of one size instead of the ramp 1, 2, 4, ...
-            flags |= 16
-        if os.environ.get('KBE_RAMP', 'classic') == 'fast':    # KBE_VIDEO_FAST_RAMP: transfer groups of 1, 3, 7, 15, ... frames
-            flags |= 1024
-        if os.environ.get('KBE_AHEAD') == '0':              # KBE_VIDEO_NO_AHEAD: every group of the fused route keeps its own placement launch
-            flags |= 512
-        flags |= fused_build_bits(video=True)               # KBE_FUSED_CAP: KBE_VIDEO_FUSED_LEAN / _ROOMY
-        if not host_out.is_cuda and batch < 0 and handoff_by_sdma():
-            flags |= 8192                                   # KBE_VIDEO_SDMA
-            if os.environ.get('KBE_INJECT_HANDOFF_FAULT') == '1':
-                flags |= 32768                              # KBE_VIDEO_INJECT_FAULT (test hook: tests/test_hip_parity.py)
-            if os.environ.get('KBE_INJECT_HANDOFF_TIMEOUT') == '1':
-                flags |= 65536                              # KBE_VIDEO_INJECT_TIMEOUT (test hook)
-        keep_flags = flags & ~base_flags                    # the switches set above, should the launch shape be taken again
-        scratch = state['scratch']
-        if group > 1:
-            # n scratch sets per lane in use, allocated on first use -- 224 MB each at 1024^2, 0.9 GB at 2048^2 (most of it the
-            # bucket / spill area): a launch shape that would take more than the budget (KBE_SCRATCH_BUDGET_MB, default half of
-            # what is free, never less than one set per lane) falls back to fewer frames per launch
-            # (asked only when the sets the cloud already holds do not do: the budget reads the device's free memory, ~10 us of every call)
-            fits = group
-            if 'scratch_groups' not in state or state['scratch_groups'].numel() < group * lanes * self.scratch_stride(state) or os.environ.get('KBE_SCRATCH_BUDGET_MB'):
-                max_sets = self.scratch_set_budget(state)
-                while fits > 1 and fits * lanes > max_sets:
-                    fits = max(1, fits // 2)
-            if fits != group:
-                flags, group, fused = self.video_launch_shape(state, cameras, batch, to_host=not host_out.is_cuda, max_group=fits)
-                flags |= keep_flags
-        state['video_sets'] = group * lanes
-        if group > 1:
-            scratch, _ = self.group_scratch(state, group * lanes)
+        # one frame per launch renders on the lanes' own sets, more on the group scratch (shape.group sets per lane, allocated on first use)
+        state['video_sets'] = shape.sets
+        scratch = self.group_scratch(state, shape.sets)[0] if shape.group > 1 else state['scratch']
         self._check(self.lib.kbe_render_video(_ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), _i(state['N']),
                                               _i(W), _i(H), _d(float(baseline)), _i(n), focals, shifts, _i(cw), _i(ch),
                                               _ptr(scratch, torch.uint8), _ptr(state['stage'], torch.uint8), _i(batch),
                                               ctypes.c_void_p(host_out.data_ptr()), _i(state['raster_w']), _i(state['raster_n']),
                                               _ptr(state['packed'], torch.uint8) if fused else None, _d(state['cloud_focal']),
-                                              _i(flags), _stream(), copy_stream, _i(lanes), lane_streams, _d(self.near_depth(state) if fused else 0.0)), 'kbe_render_video')
+                                              _i(shape.flags), _stream(), copy_stream, _i(lanes), lane_streams, _d(self.near_depth(state) if fused else 0.0)), 'kbe_render_video')
         return host_out
 
     def handoff_status(self):

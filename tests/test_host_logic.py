@@ -358,3 +358,169 @@ def test_degrid_schedule_switch_selects_the_serial_route(monkeypatch):
         _native.kernels()
     monkeypatch.delenv('KBE_DEGRID')
     assert _native.kernels() is default
+
+
+# What HipKernels.render_video passed to kbe_render_video before video_shape.call_shape existed: (case, cloud, frames, zooms out,
+# to host, batch argument, lanes chosen, switches away from their defaults, budget in sets or None) -> (batch, frames per launch,
+# flags, scratch sets).  RECORDED rows are the arguments of real calls, taken with a shim in front of the library entry on an
+# MI355X at the commit before the split (clouds of bench.build_scene); the rows marked COMPOSED could not be reached that way and
+# were put together by hand from that commit's own video_launch_shape, transfer_group and host_lanes, run on the CPU.
+_INPAINTED, _RAW, _DENSE = (1137109, 1024, 1024, True), (1048576, 1024, 1024, True), (4194304, 1024, 1024, True)
+_BUCKET512, _BUCKET768, _BUCKET1024 = (280049, 512, 512, False), (617619, 768, 768, False), (1137109, 1024, 1024, False)
+_BUDGET_SHAPE = (288 * 224, 288, 224, True)          # test_hip_parity.py::test_scratch_budget_falls_back_...: a raw 288 x 224 cloud, KBE_FUSED=1
+_SET = 1.0                                           # (any budget in MB: call_shape only asks whether the switch is set)
+_CALL_SHAPE_ROWS = [
+    # the bench default: inpainted 1024^2, delivered
+    ('bench default, 20 frames', _INPAINTED, 20, False, True, None, 2, {}, None, (-16, 12, 8544, 24)),
+    ('bench default, 75 frames', _INPAINTED, 75, False, True, None, 2, {}, None, (-18, 12, 8544, 24)),
+    ('bench default, 256 frames, two lanes', _INPAINTED, 256, False, True, None, 2, {}, None, (-32, 12, 8544, 24)),
+    ('bench default, 1024 frames (COMPOSED)', _INPAINTED, 1024, False, True, None, 2, {}, None, (-32, 12, 8544, 24)),
+    ('bench default, 1 frame', _INPAINTED, 1, False, True, None, 2, {}, None, (-1, 12, 8544, 24)),
+    ('bench default, 3 frames', _INPAINTED, 3, False, True, None, 2, {}, None, (-3, 12, 8544, 24)),
+    ('256 frames on three lanes', _INPAINTED, 256, False, True, None, 3, {}, None, (-12, 12, 8544, 36)),
+    ('256 frames on four lanes', _INPAINTED, 256, False, True, None, 4, {}, None, (-12, 12, 8544, 48)),
+    # left in HBM
+    ('left in HBM, 20 frames', _INPAINTED, 20, False, False, None, 4, {}, None, (0, 4, 6, 16)),
+    ('left in HBM, 1 frame', _INPAINTED, 1, False, False, None, 4, {}, None, (0, 4, 6, 16)),
+    ('left in HBM, batch=-8 is ignored', _INPAINTED, 20, False, False, -8, 4, {}, None, (0, 4, 6, 16)),
+    ('left in HBM, batch=8 is ignored', _INPAINTED, 20, False, False, 8, 4, {}, None, (0, 4, 6, 16)),
+    # a dolly zoom-out of a raw cloud
+    ('dolly, 20 frames to host on four lanes', _RAW, 20, True, True, None, 4, {}, None, (-8, 8, 8425, 32)),
+    ('dolly, 3 frames to host', _RAW, 3, True, True, None, 4, {}, None, (-3, 8, 8425, 32)),
+    ('dolly, 256 frames to host on two lanes', _RAW, 256, True, True, None, 2, {}, None, (-32, 8, 8425, 16)),
+    ('dolly, left in HBM', _RAW, 75, True, False, None, 4, {}, None, (0, 8, 225, 32)),
+    # a cloud denser than the raster
+    ('dense, 20 frames to host', _DENSE, 20, False, True, None, 4, {}, None, (-3, 3, 8196, 12)),
+    ('dense, left in HBM', _DENSE, 20, False, False, None, 4, {}, None, (0, 3, 4, 12)),
+    # the bucket route at three frame sizes
+    ('bucket 512^2 to host', _BUCKET512, 20, False, True, None, 4, {}, None, (-4, 4, 8198, 16)),
+    ('bucket 512^2 in HBM', _BUCKET512, 20, False, False, None, 4, {}, None, (0, 4, 6, 16)),
+    ('bucket 768^2 to host', _BUCKET768, 20, False, True, None, 2, {}, None, (-16, 2, 8194, 4)),
+    ('bucket 768^2 in HBM', _BUCKET768, 20, False, False, None, 4, {}, None, (0, 2, 2, 8)),
+    ('bucket 1024^2 to host', _BUCKET1024, 20, False, True, None, 2, {}, None, (-16, 1, 8192, 2)),
+    ('bucket 1024^2 in HBM', _BUCKET1024, 20, False, False, None, 4, {}, None, (0, 1, 0, 4)),
+    # an explicit batch
+    ('batch=0: per-frame delivery', _INPAINTED, 20, False, True, 0, 2, {}, None, (0, 12, 352, 24)),
+    ('batch=-8', _INPAINTED, 20, False, True, -8, 2, {}, None, (-8, 12, 8544, 24)),
+    ('batch=8: the staged ring', _INPAINTED, 20, False, True, 8, 2, {}, None, (8, 1, 0, 2)),
+    ('batch=8 on the bucket route', _BUCKET512, 20, False, True, 8, 4, {}, None, (8, 1, 0, 4)),
+    ('batch=0 on the bucket route', _BUCKET512, 20, False, True, 0, 4, {}, None, (0, 4, 6, 16)),
+    # each switch away from its default, one at a time
+    ('KBE_FILL_DIST=1 to host', _INPAINTED, 20, False, True, None, 2, {'fill_dist': True}, None, (-16, 8, 8425, 16)),
+    ('KBE_FILL_DIST=1 in HBM', _INPAINTED, 20, False, False, None, 4, {'fill_dist': True}, None, (0, 8, 225, 32)),
+    ('KBE_FILL_DIST=0, dolly', _RAW, 75, True, True, None, 4, {'fill_dist': False}, None, (-12, 12, 8544, 48)),
+    ('KBE_FILL_GROUP=3 to host', _INPAINTED, 20, False, True, None, 2, {'fill_group': 3}, None, (-16, 3, 8196, 6)),
+    ('KBE_FILL_GROUP=7 in HBM', _INPAINTED, 20, False, False, None, 4, {'fill_group': 7}, None, (0, 7, 192, 28)),
+    ('KBE_FILL_GROUP=40 in HBM', _INPAINTED, 20, False, False, None, 4, {'fill_group': 40}, None, (0, 12, 352, 48)),
+    ('KBE_FILL_GROUP=7, dolly', _RAW, 75, True, True, None, 4, {'fill_group': 7}, None, (-7, 7, 8393, 28)),
+    ('KBE_HOST_LANES=1', _INPAINTED, 20, False, True, None, 1, {'host_lanes': 1}, None, (-16, 12, 8544, 12)),
+    ('KBE_HOST_LANES=3', _INPAINTED, 20, False, True, None, 3, {'host_lanes': 3}, None, (-12, 12, 8544, 36)),
+    ('KBE_HOST_LANES=1, dolly', _RAW, 75, True, True, None, 1, {'host_lanes': 1}, None, (-32, 8, 8425, 8)),
+    ('KBE_DELIVERY_BATCH=-4', _INPAINTED, 20, False, True, None, 2, {'delivery_batch': -4}, None, (-4, 12, 8544, 24)),
+    ('KBE_DELIVERY_BATCH=6', _INPAINTED, 20, False, True, None, 2, {'delivery_batch': 6}, None, (6, 1, 0, 2)),
+    ('KBE_DELIVERY_BATCH=6, dolly', _RAW, 75, True, True, None, 4, {'delivery_batch': 6}, None, (6, 1, 9, 4)),
+    ('KBE_DELIVERY_BATCH=-4 in HBM', _INPAINTED, 20, False, False, None, 4, {'delivery_batch': -4}, None, (0, 4, 6, 16)),
+    ('KBE_RAMP=fast to host', _INPAINTED, 20, False, True, None, 2, {'fast_ramp': True}, None, (-16, 12, 9568, 24)),
+    ('KBE_RAMP=fast in HBM', _INPAINTED, 20, False, False, None, 4, {'fast_ramp': True}, None, (0, 4, 1030, 16)),
+    ('KBE_FREE_TRANSFERS=1 to host', _INPAINTED, 20, False, True, None, 2, {'free_transfers': True}, None, (-16, 12, 8552, 24)),
+    ('KBE_FREE_TRANSFERS=1 in HBM', _INPAINTED, 20, False, False, None, 4, {'free_transfers': True}, None, (0, 4, 6, 16)),
+    ('KBE_FREE_TRANSFERS=0, dolly', _RAW, 75, True, True, None, 4, {'free_transfers': False}, None, (-8, 8, 8417, 32)),
+    ('KBE_EVEN_GROUPS=1 to host', _INPAINTED, 20, False, True, None, 2, {'even_groups': True}, None, (-16, 12, 8560, 24)),
+    ('KBE_EVEN_GROUPS=1 in HBM', _INPAINTED, 20, False, False, None, 4, {'even_groups': True}, None, (0, 4, 22, 16)),
+    ('KBE_AHEAD=0 to host', _INPAINTED, 20, False, True, None, 2, {'no_ahead': True}, None, (-16, 12, 9056, 24)),
+    ('KBE_AHEAD=0 in HBM', _INPAINTED, 20, False, False, None, 4, {'no_ahead': True}, None, (0, 4, 518, 16)),
+    ('KBE_FUSED_CAP=lean to host', _INPAINTED, 20, False, True, None, 2, {'build_bits': 2048}, None, (-16, 12, 10592, 24)),
+    ('KBE_FUSED_CAP=roomy in HBM', _INPAINTED, 20, False, False, None, 4, {'build_bits': 4096}, None, (0, 4, 4102, 16)),
+    ('KBE_HANDOFF=blit', _INPAINTED, 20, False, True, None, 2, {'sdma': False}, None, (-16, 12, 352, 24)),
+    ('KBE_HANDOFF=blit, dolly', _RAW, 75, True, True, None, 4, {'sdma': False}, None, (-8, 8, 233, 32)),
+    ('KBE_INJECT_HANDOFF_FAULT=1 (COMPOSED)', _INPAINTED, 20, False, True, None, 2, {'inject_fault': True}, None, (-16, 12, 8544 | 32768, 24)),
+    ('KBE_INJECT_HANDOFF_TIMEOUT=1 (COMPOSED)', _INPAINTED, 20, False, True, None, 2, {'inject_timeout': True}, None, (-16, 12, 8544 | 65536, 24)),
+    ('the hooks need the SDMA hand-off (COMPOSED)', _INPAINTED, 20, False, True, None, 2, {'inject_fault': True, 'inject_timeout': True, 'sdma': False}, None, (-16, 12, 352, 24)),
+    ('the hooks, per-frame delivery (COMPOSED)', _INPAINTED, 20, False, True, 0, 2, {'inject_fault': True, 'inject_timeout': True}, None, (0, 12, 352, 24)),
+    ('the hooks, left in HBM (COMPOSED)', _INPAINTED, 20, False, False, None, 4, {'inject_fault': True, 'inject_timeout': True}, None, (0, 4, 6, 16)),
+    # KBE_SCRATCH_BUDGET_MB; the transfer group (batch) stays that of the uncut shape
+    ('budget 9 sets, two lanes', _INPAINTED, 20, False, True, None, 2, {'scratch_budget_mb': _SET}, 9, (-16, 3, 8196, 6)),
+    ('budget 9 sets, in HBM', _INPAINTED, 20, False, False, None, 4, {'scratch_budget_mb': _SET}, 9, (0, 2, 2, 8)),
+    ('budget 9 sets, four lanes to host', _INPAINTED, 20, False, True, None, 4, {'scratch_budget_mb': _SET}, 9, (-12, 1, 8192, 4)),
+    ('budget < 1 set, two lanes', _INPAINTED, 20, False, True, None, 2, {'scratch_budget_mb': _SET}, 4, (-16, 1, 8192, 2)),
+    ('budget < 1 set, in HBM', _INPAINTED, 20, False, False, None, 4, {'scratch_budget_mb': _SET}, 4, (0, 1, 0, 4)),
+    ('budget 21 sets, two lanes', _INPAINTED, 20, False, True, None, 2, {'scratch_budget_mb': _SET}, 21, (-16, 6, 8352, 12)),
+    ('budget 21 sets, in HBM: not binding', _INPAINTED, 20, False, False, None, 4, {'scratch_budget_mb': _SET}, 21, (0, 4, 6, 16)),
+    ('budget 21 sets, four lanes to host', _INPAINTED, 20, False, True, None, 4, {'scratch_budget_mb': _SET}, 21, (-12, 3, 8196, 12)),
+    ('budget 9 sets, dolly', _RAW, 75, True, True, None, 4, {'scratch_budget_mb': _SET}, 9, (-8, 2, 8203, 8)),
+    ('budget < 1 set, dolly', _RAW, 75, True, True, None, 4, {'scratch_budget_mb': _SET}, 4, (-8, 1, 8201, 4)),
+    ('budget 21 sets, dolly', _RAW, 75, True, True, None, 4, {'scratch_budget_mb': _SET}, 21, (-8, 4, 8207, 16)),
+    # the shape of the GPU test of the budget, whose assertions are 8 and 4 sets (COMPOSED)
+    ('GPU budget test, no budget (COMPOSED)', _BUDGET_SHAPE, 40, True, False, None, 4, {}, None, (0, 8, 225, 32)),
+    ('GPU budget test, nine sets (COMPOSED)', _BUDGET_SHAPE, 40, True, False, None, 4, {'scratch_budget_mb': _SET}, 9, (0, 2, 3, 8)),
+    ('GPU budget test, less than one set (COMPOSED)', _BUDGET_SHAPE, 40, True, False, None, 4, {'scratch_budget_mb': _SET}, 4, (0, 1, 1, 4)),
+]
+
+
+@pytest.mark.parametrize('row', _CALL_SHAPE_ROWS, ids=[r[0] for r in _CALL_SHAPE_ROWS])
+def test_call_shape_passes_what_render_video_passed(row):
+    """video_shape.call_shape on plain values: all six fields of the call's shape against the table above."""
+    from ken_burns_effect_amd import video_shape
+    _, (N, W, H, fused), n, zooms_out, to_host, batch, lanes, switches, budget, (want_batch, want_group, want_flags, want_sets) = row
+    sw = video_shape.DEFAULTS._replace(**switches)
+    budget_sets = (lambda: 1 << 20) if budget is None else (lambda: budget)        # (no switch: half of a device's free memory, never binding here)
+    got = video_shape.call_shape(N, W, H, fused, n, zooms_out, to_host, batch, lanes, sw, 0, budget_sets)
+    assert got == video_shape.CallShape(lanes=lanes, batch=want_batch, group=want_group, flags=want_flags, fused=fused, sets=want_sets)
+    assert got.sets == got.group * got.lanes
+
+
+def test_call_shape_asks_for_the_budget_only_when_it_has_to():
+    """The budget reads the device's free memory (~10 us of a call): not asked while the sets the cloud holds do and
+    KBE_SCRATCH_BUDGET_MB is unset, nor when one frame per launch renders on the lanes' own sets."""
+    from ken_burns_effect_amd import video_shape
+    asked = []
+
+    def budget():
+        asked.append(1)
+        return 1 << 20
+    shape = lambda cloud, to_host, lanes, held, sw=video_shape.DEFAULTS, batch=None: video_shape.call_shape(      # noqa: E731
+        *cloud, 20, False, to_host, batch, lanes, sw, held, budget)
+    assert shape(_INPAINTED, True, 2, 24).sets == 24 and shape(_INPAINTED, False, 4, 48).sets == 16 and not asked
+    assert shape(_BUCKET1024, False, 4, 0).sets == 4 and shape(_INPAINTED, True, 2, 0, batch=8).sets == 2 and not asked
+    assert shape(_INPAINTED, True, 2, 23).sets == 24 and len(asked) == 1
+    assert shape(_INPAINTED, True, 2, 0).sets == 24 and len(asked) == 2
+    assert shape(_INPAINTED, True, 2, 24, video_shape.DEFAULTS._replace(scratch_budget_mb=1e6)).sets == 24 and len(asked) == 3
+
+
+def test_video_switches_reads_the_environment_once_into_a_record(monkeypatch):
+    """_native.video_switches: every switch of a video call, parsed; unset = video_shape.DEFAULTS; read per call."""
+    from ken_burns_effect_amd import _native, video_shape
+    names = ('KBE_FILL_DIST', 'KBE_FILL_GROUP', 'KBE_HOST_LANES', 'KBE_DELIVERY_BATCH', 'KBE_RAMP', 'KBE_FREE_TRANSFERS', 'KBE_EVEN_GROUPS', 'KBE_AHEAD',
+             'KBE_FUSED_CAP', 'KBE_HANDOFF', 'KBE_INJECT_HANDOFF_FAULT', 'KBE_INJECT_HANDOFF_TIMEOUT', 'KBE_SCRATCH_BUDGET_MB')
+    for k in names:
+        monkeypatch.delenv(k, raising=False)
+    assert _native.video_switches() == video_shape.DEFAULTS
+    cases = [('KBE_FILL_DIST', '1', {'fill_dist': True}), ('KBE_FILL_DIST', '0', {'fill_dist': False}), ('KBE_FILL_DIST', 'auto', {}),
+             ('KBE_FILL_GROUP', '7', {'fill_group': 7}), ('KBE_FILL_GROUP', '', {}), ('KBE_HOST_LANES', '3', {'host_lanes': 3}), ('KBE_HOST_LANES', '0', {'host_lanes': 0}),
+             ('KBE_DELIVERY_BATCH', '-4', {'delivery_batch': -4}), ('KBE_RAMP', 'fast', {'fast_ramp': True}), ('KBE_RAMP', 'classic', {}),
+             ('KBE_FREE_TRANSFERS', '1', {'free_transfers': True}), ('KBE_FREE_TRANSFERS', '0', {'free_transfers': False}), ('KBE_EVEN_GROUPS', '1', {'even_groups': True}),
+             ('KBE_AHEAD', '0', {'no_ahead': True}), ('KBE_AHEAD', '1', {}), ('KBE_FUSED_CAP', 'lean', {'build_bits': _native.KBE_VIDEO_FUSED_LEAN}),
+             ('KBE_FUSED_CAP', 'roomy', {'build_bits': _native.KBE_VIDEO_FUSED_ROOMY}), ('KBE_HANDOFF', 'blit', {'sdma': False}), ('KBE_HANDOFF', 'sdma', {}),
+             ('KBE_INJECT_HANDOFF_FAULT', '1', {'inject_fault': True}), ('KBE_INJECT_HANDOFF_TIMEOUT', '1', {'inject_timeout': True}),
+             ('KBE_SCRATCH_BUDGET_MB', '1', {'scratch_budget_mb': 1.0}), ('KBE_SCRATCH_BUDGET_MB', '0', {'scratch_budget_mb': 0.0})]
+    for name, value, fields in cases:
+        monkeypatch.setenv(name, value)
+        assert _native.video_switches() == video_shape.DEFAULTS._replace(**fields), (name, value)
+        monkeypatch.delenv(name)
+    assert set(names) == {c[0] for c in cases}
+    monkeypatch.setenv('KBE_FUSED_CAP', 'lean')
+    assert _native.fused_build_bits() == _native.KBE_STAGE_FUSED_LEAN and _native.fused_build_bits(video=True) == _native.KBE_VIDEO_FUSED_LEAN
+    monkeypatch.delenv('KBE_FUSED_CAP')
+    monkeypatch.setenv('KBE_DELIVERY_BATCH', 'many')
+    with pytest.raises(_native.KbeError, match="KBE_DELIVERY_BATCH='many' is not an integer"):
+        _native.video_switches()
+
+
+def test_the_shape_of_a_call_is_decided_without_gpu_library_or_environment():
+    """video_shape is plain Python on plain values: no torch, no ctypes, no os."""
+    import ast
+    from ken_burns_effect_amd import video_shape
+    tree = ast.parse(open(video_shape.__file__).read())
+    imported = {a.name.split('.')[0] for node in ast.walk(tree) if isinstance(node, ast.Import) for a in node.names}
+    imported |= {(node.module or '').split('.')[0] for node in ast.walk(tree) if isinstance(node, ast.ImportFrom)}
+    assert imported == {'collections'}
