@@ -1,10 +1,12 @@
-// The launch plan of kbe_render_video (kbe_frame.hip): which lane renders which frames in which launch, into which scratch set
-// and which destination slot, and how the frames leave -- decided on indices alone, before anything is enqueued.  Plain C++ (no
-// HIP): tests/video_plan_check.cpp checks its invariants on the host.
+// The launch plan of kbe_render_video (kbe_frame.hip; its frames leave through kbe_handoff.hip): which lane renders which frames in
+// which launch, into which scratch set and which destination slot, and how the frames leave -- decided on indices alone, before
+// anything is enqueued -- and the layout of `stage`, which those slots index.  Plain C++ (no HIP): tests/video_plan_check.cpp checks
+// its invariants on the host.
 #pragma once
+#include <stddef.h>
 #include <vector>
 
-namespace {
+namespace kbe {
 
 enum class VideoDest {
     HBM,            // host_out is device memory: every frame's last kernel stores straight into host_out[i]
@@ -13,6 +15,23 @@ enum class VideoDest {
     RING,           // batch > 0: round 1's staged ring, two halves of `batch` frames
 };
 enum { PLAN_ZBUF_ALONE = 0, PLAN_ZBUF_A = 1, PLAN_ZBUF_B = 2 };      // the bucket route's z-buffers (KBE_STAGE_ZBUF_*; 0: stand-alone)
+
+// stage = [raw_per_lane * lanes raw frames][lanes * fin finished frames][ring half 0: batch frames][ring half 1: batch frames]
+// [turn counter of the hand-off: 256 bytes, 256-byte aligned].  The raw frames are those of a cropped video in front of the crop (a
+// launch takes up to raw_per_lane = KBE_FRAME_JOBS frames); PlanFrame::slot indexes the finished frames or the ring.
+struct StageLayout {
+    size_t fb;              // bytes of a frame
+    int fin;                // finished-frame buffers per lane: two, or a whole transfer group's
+    size_t raw_per_lane, finished, ring, ctl, total;    // the regions' byte offsets (raw frames: 0), and kbe_video_stage_bytes
+    size_t raw(int lane, int j) const { return (raw_per_lane * lane + j) * fb; }        // frame j of the lane's launch
+};
+inline StageLayout stage_layout(int W, int H, int lanes, int batch, int raw_per_lane)
+{
+    const size_t fb = (size_t) W * H * 3, fin = batch < -2 ? -batch : 2;
+    const size_t finished = (size_t) raw_per_lane * lanes * fb, ring = finished + fin * lanes * fb;
+    const size_t ctl = (ring + 2 * (size_t) (batch > 0 ? batch : 0) * fb + 255) & ~(size_t) 255;
+    return StageLayout{ fb, (int) fin, (size_t) raw_per_lane, finished, ring, ctl, ctl + 256 };
+}
 
 struct VideoPlanIn {
     int n_frames, lanes, group, batch;  // group: frames per launch (KBE_VIDEO_GROUP / _FILL_GROUP); batch: kbe_render_video's
@@ -137,4 +156,4 @@ VideoPlan plan_video(const VideoPlanIn& in, CanPlaceAhead can_place_ahead)
     return p;
 }
 
-}  // namespace
+}  // namespace kbe

@@ -1,4 +1,5 @@
-// Host-side checker of kbe_render_video's launch plan (ken-burns-effect_amd/csrc/kbe_video_plan.h), run by tests/test_video_plan.py.
+// Host-side checker of kbe_render_video's launch plan and stage layout (ken-burns-effect_amd/csrc/kbe_video_plan.h), run by
+// tests/test_video_plan.py.
 //   video_plan_check                  every invariant over a sweep of videos; prints "<plans checked> <failures>"
 //   video_plan_check DEST N LANES GROUP BATCH FLAGS
 //                                     prints one plan: a "unit LANE FIRST COUNT" line per unit, then its launches as
@@ -10,11 +11,16 @@
 
 #include "kbe_video_plan.h"
 
+using namespace kbe;
+
 static bool can_place_ahead(int n, int n_next) { return n + n_next <= 14; }     // a stand-in for fused_can_place_ahead: some pairs may not
+
+static const int RAW_PER_LANE = 12;                 // the most frames a launch takes (kbe_tiles.h: KBE_FRAME_JOBS; the sweep's groups go up to it)
+static StageLayout layout_of(int lanes, int batch) { return stage_layout(5 + lanes, 3, lanes, batch, RAW_PER_LANE); }      // (frames of an odd size)
 
 static VideoPlanIn make_in(int dest, int n, int lanes, int group, int batch, int flags)
 {
-    const int fin = batch < -2 ? -batch : 2;        // kbe_frame.hip: stage_fin_per_lane
+    const int fin = layout_of(lanes, batch).fin;
     return VideoPlanIn{ n, lanes, group, batch, (VideoDest) dest, fin, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (flags & 8) != 0 };
 }
 
@@ -71,6 +77,19 @@ static void check(const VideoPlanIn& in, int flags)
         }
         CHECK(expect == un.first + un.count, "unit %d's launches do not cover it", u);
     }
+    // the stage: its regions in order, without gaps or overlap, the turn counter 256-byte aligned behind the last frame; every slot's
+    // frame, and every raw frame of a launch, wholly inside its region
+    const StageLayout L = layout_of(in.lanes, in.batch);
+    const size_t ring_end = L.ring + 2 * (size_t) (in.batch > 0 ? in.batch : 0) * L.fb;
+    CHECK(L.fin == in.fin && L.raw(in.lanes - 1, RAW_PER_LANE - 1) + L.fb == L.finished && L.finished + (size_t) L.fin * in.lanes * L.fb == L.ring, "stage regions");
+    CHECK(L.ctl >= ring_end && L.ctl < ring_end + 256 && L.ctl % 256 == 0 && L.total == L.ctl + 256, "turn counter at %zu", L.ctl);
+    for (const PlanLaunch& la : p.launches)
+        for (int j = 0; j < la.count; j++) {
+            const PlanFrame& f = p.frames[la.first + j];
+            CHECK(L.raw(la.lane, j) + L.fb <= L.finished, "frame %d: raw frame outside its region", f.frame);
+            const size_t lo = in.dest == VideoDest::RING ? L.ring : L.finished, hi = in.dest == VideoDest::RING ? ring_end : L.ring;
+            if (in.dest != VideoDest::HBM) CHECK(f.slot >= 0 && lo + ((size_t) f.slot + 1) * L.fb <= hi, "frame %d: slot %d outside its region of the stage", f.frame, f.slot);
+        }
     CHECK(next_first == in.n_frames, "the units cover %d of %d frames", next_first, in.n_frames);
     CHECK(next_launch == (int) p.launches.size(), "launches outside every unit");
     // turns count a set's uses; the bucket route's z-buffers: every frame splats into a clear one, and A is clear at the end
