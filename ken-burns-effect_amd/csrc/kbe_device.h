@@ -24,20 +24,12 @@ constexpr int kWave = 64;   // CDNA wavefront
 __device__ __forceinline__ uint32_t zkey_encode(float f)
 {
     const uint32_t b = __float_as_uint(f);
-#if defined(KBE_KEY_SELECT) && KBE_KEY_SELECT
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-#else
     return b ^ ((uint32_t) ((int32_t) b >> 31) | 0x80000000u);          // sign set: ^ 0xFFFFFFFF, clear: ^ 0x80000000
-#endif
 }
 
 __device__ __forceinline__ float zkey_decode(uint32_t k)
 {
-#if defined(KBE_KEY_SELECT) && KBE_KEY_SELECT
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-#else
     return __uint_as_float(k ^ ~((uint32_t) ((int32_t) k >> 31) & 0x7FFFFFFFu));        // top bit set: ^ 0x80000000, clear: ^ 0xFFFFFFFF
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -107,9 +99,6 @@ __device__ __forceinline__ bool project_xy(const Camera& cam, float px, float py
     // :453 (also covers :461).  `(double) pz >= 0.001` in fp32: 0.001f is the smallest float that is >= the double 0.001
     if (!(pz >= 0.001f)) return false;
     const float lvx = 0.0f - px, lvy = 0.0f - py, lvz = 0.0f - pz;
-#if defined(KBE_DIV_FAST) && !KBE_DIV_FAST
-    const float dist = (cam.focal_f - pz) / lvz;               // :457-459
-#else
     // :457-459.  pz >= 0.001 here; F - pz is 0 or at least half an ulp of the smaller of the two (>= 2^-34): with pz and
     // F below 2^100 -- one test for the wave -- div_unscaled IS the division
     float dist;
@@ -117,7 +106,6 @@ __device__ __forceinline__ bool project_xy(const Camera& cam, float px, float py
     const bool f_small = fabsf(cam.focal_f) < 1.0e30f;             // uniform; loop-invariant where a wave places several units
     if (f_small && __ballot(!(pz < 1.0e30f)) == 0ull) dist = div_unscaled(num, lvz);
     else dist = num / lvz;
-#endif
     const float ix = __builtin_fmaf(dist, lvx, px);            // :465 as NVRTC (--fmad=true) emits it
     const float iy = __builtin_fmaf(dist, lvy, py);
     if (cam.fp32_centre) {                                     // wave-uniform; the normal case

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "kbe_cloud.h"
+#include "kbe_fused_plan.h"
 #include "kbe_tiles.h"
 
 using namespace kbe;
@@ -86,8 +87,8 @@ struct PlaceArgs {          // the placement of one frame: its camera, and where
 };
 
 // what a tile launch takes: the cloud, up to J frames to render, and up to J frames whose placements it makes AHEAD -- the
-// work of k_place for the frames the NEXT tile launch on this stream renders (they use the other bank of their scratch sets)
-// (KBE_SHARED_LISTS) consecutive frames of a launch share candidate lists in SUB-GROUPS: frame k reads the lists of its sub-group's
+// work of k_place for the frames the NEXT tile launch on this stream renders (they use the other bank of their scratch sets).
+// Consecutive frames of a launch share candidate lists in SUB-GROUPS: frame k reads the lists of its sub-group's
 // lead (itself: lists of its own), and a sub-group's tiles zero the shared counter when the last of its frames has
 // read it; of the frames placed ahead, frame k that leads a sub-group k .. last > k makes the lists for those frames
 // (the box of a sub-block's corners under cameras k and nx_last[k], widened by `dev`: how far the cameras in between stray from
@@ -214,31 +215,16 @@ __device__ __forceinline__ int row_min(int v)
 // In two steps, so that a caller can do other work while the list atomic is under way: place_point_begin returns the list entry
 // the lane owes -- the tile and the slot its atomic returned -- and place_point_end writes it.
 struct ListSlot { int t, pos; };
-// Whose candidate list a placement feeds (KBE_SHARED_LISTS; wave-uniform).  mode 0: the frame's own.  The frames a launch places
-// ahead are consecutive cameras of a path -- same focal length, shifts on one line (the host checks: launch_frames_fused) -- and
+// Whose candidate list a placement feeds (wave-uniform).  mode 0: the frame's own.  The frames a launch places
+// ahead are consecutive cameras of a path -- same focal length, shifts on one line (the host checks: kbe_fused_plan.h) -- and
 // list almost the same sub-blocks for the same tiles: the group then shares ONE set of lists, made by the row of its first
 // frame (mode 2) from the box of the sub-block's corners under the group's FIRST and LAST camera (a point's position is a
 // ratio of two functions linear in the step: monotone between the two, so every frame in between stays inside; SHARE_MARGIN
 // pixels cover the rounding of the frames' own fp32 arithmetic and of the shifts), and the other rows make none (mode 1).
-#ifndef KBE_SHARED_LISTS
-#define KBE_SHARED_LISTS 1
-#endif
-#ifndef KBE_SHARE_MAX_PX
-#define KBE_SHARE_MAX_PX 13.0       // (launch_frames_fused: share_plan)
-#endif
 // 32-bit byte offsets on the launch's uniform bases (placements, points, colours): with a signed index every such address was a
 // sign extension, a 64-bit multiply-add and a 64-bit add.  The route takes at most 2^28 points (KBE_FUSED_MAX_POINTS): x 16 fits.
-#ifndef KBE_OFFSETS_32
-#define KBE_OFFSETS_32 1
-#endif
-template <class T> __device__ __forceinline__ T* at_offset32(T* base, uint32_t index)
-{
-    return KBE_OFFSETS_32 ? (T*) ((char*) base + index * (uint32_t) sizeof(T)) : base + (int) index;
-}
-template <class T> __device__ __forceinline__ const T* at_offset32(const T* base, uint32_t index)
-{
-    return KBE_OFFSETS_32 ? (const T*) ((const char*) base + index * (uint32_t) sizeof(T)) : base + (int) index;
-}
+template <class T> __device__ __forceinline__ T* at_offset32(T* base, uint32_t index) { return (T*) ((char*) base + index * (uint32_t) sizeof(T)); }
+template <class T> __device__ __forceinline__ const T* at_offset32(const T* base, uint32_t index) { return (const T*) ((const char*) base + index * (uint32_t) sizeof(T)); }
 struct ShareMode { int mode; float dsx, dsy, dsz, dev_x, dev_y, dev_z; };      // ds: the sub-group's last camera's shift minus this (its first) one's; dev: FrameJobsT::dev
 constexpr float SHARE_MARGIN = 0.25f;
 __device__ __forceinline__ ListSlot place_point_begin(const CloudPoint& p, int i, int lane, const Camera& cam, int tiles_x, int tiles_y, Placement* place,
@@ -257,8 +243,8 @@ __device__ __forceinline__ ListSlot place_point_begin(const CloudPoint& p, int i
     pl.err = project_err_fast(cam, ok ? z : 1024.0f);
     *at_offset32(place, (uint32_t) i) = pl;
     int nex = nwx, ney = nwy;                                   // the corner's range over the frames the list serves: [nwx, nex] x [nwy, ney]
-    if (KBE_SHARED_LISTS && share.mode == 1) return owed;       // uniform
-    if (KBE_SHARED_LISTS && share.mode == 2) {
+    if (share.mode == 1) return owed;                           // uniform
+    if (share.mode == 2) {
         // the point under the group's last camera, to the accuracy a box needs (a reciprocal instead of the division)
         const float xb = x + share.dsx, yb = y + share.dsy, zb = z + share.dsz;
         const bool seen_b = zb >= 0.001f;
@@ -381,20 +367,13 @@ typedef const __attribute__((address_space(4))) FrameArgs* FrameArgsPtr;
 typedef const __attribute__((address_space(4))) PlaceArgs* PlaceArgsPtr;
 typedef const __attribute__((address_space(4))) PackedCloud* PackedCloudPtr;
 
-// where in the tile's life its share of the NEXT frames' placements is made (place_ahead below): 0 = at the end, behind the
-// epilogue's stores; 1 = behind the splat, in front of the barrier that ends it; 2, 3 = the first KBE_AHEAD_UNITS units of a
-// wave up front -- their points requested with the tile's list, placed while the tile's own points are under way, the list
-// entries written in front of (2) or behind (3) the splat -- and what is left at the end
-#ifndef KBE_AHEAD_AT
-#define KBE_AHEAD_AT 3
+// where in the tile's life its share of the NEXT frames' placements is made (place_ahead below): the first KBE_AHEAD_UNITS units
+// of a wave up front -- their points requested with the tile's list, placed while the tile's own points are under way, the list
+// entries written behind the splat -- and what is left at the end, behind the epilogue's stores
+constexpr int AHEAD_UNITS = KBE_AHEAD_UNITS;     // (kbe_fused_plan.h)
+#ifndef KBE_SPLAT_DEPTH
+#define KBE_SPLAT_DEPTH 4       // steps of the candidate list whose operands a wave requests before it works on the first (frame_body)
 #endif
-#ifndef KBE_AHEAD_UNITS
-#define KBE_AHEAD_UNITS 3       // (a wave's share of an equal group is 2.17 units: with three up front nothing is left for the end; 17.9 -> 17.6 us per frame)
-#endif
-constexpr int AHEAD_UNITS = KBE_AHEAD_AT >= 2 ? KBE_AHEAD_UNITS : 0;
-#ifndef KBE_LAZY_COLOURS
-#define KBE_LAZY_COLOURS 2      // colours fetched for the records only, behind the splat (see frame_body): 0 never, 1 always,
-#endif                          // 2 in the launch for dense clouds (measured: 1024^2 inpaint cloud +3 %, 2048^2 with 16.8 M points -4 %)
 
 __device__ __forceinline__ Camera load_camera(const __attribute__((address_space(4))) Camera* c)
 {
@@ -413,7 +392,7 @@ __device__ __forceinline__ Camera load_camera(const __attribute__((address_space
 template <class Jobs> __device__ __forceinline__ ShareMode share_mode(const __attribute__((address_space(4))) Jobs* jp, int j, bool shared)
 {
     ShareMode m = { 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-    if (KBE_SHARED_LISTS && shared) {
+    if (shared) {
         const uint32_t sh = jp->nx_share[j];                            // uniform (a scalar load)
         const int lead = (int) (sh & 255u), last = (int) (sh >> 8);
         if (last > lead) {
@@ -455,6 +434,40 @@ template <class Jobs> __device__ __forceinline__ void place_ahead(const __attrib
     }
 }
 
+// The tile's z-buffer (tile + halo) holds KEYS in L.zpre until the splat is complete.  Every bin's list and every z emptied, four
+// entries per store: 294 ds_write_b128 for the workgroup, one per thread and a second one for 38 of them, instead of 1 173 single
+// stores in two loops of three trips with their bound tests -- a wave's ~25 vector instructions become ~8, on a launch bound by
+// vector issue
+template <class LDS> __device__ __forceinline__ void lds_empty_tile(LDS& L, int tid)
+{
+    constexpr int HEAD4 = (int) (sizeof(L.head) / 16), ZK4 = KH * KW / 4;
+    static_assert((KH * KW) % 4 == 0 && offsetof(LDS, head) % 16 == 0 && offsetof(LDS, zpre) % 16 == 0 && sizeof(L.head) % 16 == 0 &&
+                  HEAD4 <= TILE_THREADS && HEAD4 + ZK4 <= 2 * TILE_THREADS && ZK4 >= TILE_THREADS - HEAD4, "four entries per store");
+    uint4* const zk4 = (uint4*) L.zpre;
+    const int4 nul4 = make_int4(LDS::kNull, LDS::kNull, LDS::kNull, LDS::kNull);
+    const uint4 emp4 = make_uint4(KBE_ZKEY_EMPTY, KBE_ZKEY_EMPTY, KBE_ZKEY_EMPTY, KBE_ZKEY_EMPTY);               // common.py:430
+    if (tid < HEAD4) ((int4*) L.head)[tid] = nul4;
+    else zk4[tid - HEAD4] = emp4;
+    if (tid < ZK4 - (TILE_THREADS - HEAD4)) zk4[TILE_THREADS - HEAD4 + tid] = emp4;
+}
+// keys -> floats in place (a pixel outside the image was never splatted: it reads 1e6 like common.py:430), and the
+// one decision per tile whether the fp32-only degrid and z test apply (lds_tile_is_fast)
+template <class LDS> __device__ __forceinline__ void lds_decode_z(LDS& L, int tid, int lane)
+{
+    constexpr int ZK4 = KH * KW / 4;
+    bool band = true;
+    // four keys per thread (the first 153 threads); the band test on the keys, which order as the floats do: smallest and
+    // largest of the four against the keys of the band's ends
+    if (tid < ZK4) {
+        const uint4 k = ((const uint4*) L.zpre)[tid];
+        ((float4*) L.zpre)[tid] = make_float4(zkey_decode(k.x), zkey_decode(k.y), zkey_decode(k.z), zkey_decode(k.w));
+        const uint32_t lo = min(min(k.x, k.y), min(k.z, k.w)), hi = max(max(k.x, k.y), max(k.z, k.w));
+        band = (lo >= zkey_encode(524288.0f)) & (hi <= zkey_encode(1000000.0f));          // degrid_fast_ok of all four
+    }
+    const unsigned long long odd = __ballot(!band);
+    if (lane == 0) L.odd_z[tid >> 6] = odd != 0ull;
+}
+
 // AHEAD: a launch that also makes placements (k_frame_ahead, k_frame_group_ahead: kernels of their own, so that a launch
 // that places nothing carries none of it and profiles tell the two apart)
 // UNITS: how many of a wave's units of the next frames' placement are requested with the tile's list and placed up front (the
@@ -464,7 +477,8 @@ template <class Jobs> __device__ __forceinline__ void place_ahead(const __attrib
 template <int J, bool AHEAD, int UNITS = AHEAD_UNITS, int CAP = REC_CAP>
 __device__ __forceinline__ void frame_body(const __attribute__((address_space(4))) FrameJobsT<J>* jp, int job)
 {
-    constexpr bool LAZY = KBE_LAZY_COLOURS == 1 || (KBE_LAZY_COLOURS == 2 && UNITS > AHEAD_UNITS);
+    // colours fetched for the records only, behind the splat, in the launch for dense clouds (measured: 1024^2 inpaint cloud +3 %, 2048^2 with 16.8 M points -4 %)
+    constexpr bool LAZY = UNITS > AHEAD_UNITS;
     FrameArgsPtr ap = (FrameArgsPtr) jp->a + job;
     PackedCloudPtr pcp = &jp->pc;
     typedef TileLdsT<CAP> Lds;
@@ -495,9 +509,6 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
     // WITHOUT waiting for the count: entries past it are stale ids or whatever the scratch held, so they are clamped to the
     // cloud and the count decides later which steps exist.  None of these loads sits under a branch: a load under a branch
     // makes every later wait a wait for everything (kbe_frame.hip, k_tiles).
-#ifndef KBE_SPLAT_DEPTH
-#define KBE_SPLAT_DEPTH 4
-#endif
     constexpr int DEPTH = KBE_SPLAT_DEPTH, SUBS_PER_STEP = 64 / kCloudSub;
     int* const tile_count = ap->tile_count;
     const int count = tile_count[tile * CNT_STRIDE];
@@ -516,16 +527,11 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
 #pragma unroll
         for (int d = 0; d < DEPTH; d++) {
             ix[d] = (int) (min((uint32_t) ent[d], last_sub) * kCloudSub) + (lane & (kCloudSub - 1));
-#if KBE_OFFSETS_32
             // (32-bit byte offsets on the launch's uniform bases: as `place[ix]` with a signed index every address was a sign extension,
             // a 64-bit multiply-add and a 64-bit add; the packed cloud holds at most 2^26 points -- cloud_open -- so x 16 fits)
             const uint32_t o16 = (uint32_t) ix[d] << 4;
             pl[d] = *(const Placement*) ((const char*) place + (o16 - (o16 >> 2)));
             if (!LAZY) cc[d] = *(const CloudColour*) ((const char*) colours + o16);
-#else
-            pl[d] = place[ix[d]];
-            if (!LAZY) cc[d] = colours[ix[d]];
-#endif
         }
     };
     fetch_entries(wave);
@@ -533,8 +539,8 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
     // addresses clamped: a row with no frame to place reads the cloud's first block)
     constexpr int NU = AHEAD ? UNITS : 0;
     const int n_next = AHEAD ? jp->n_next : 0;
-    // (KBE_SHARED_LISTS) bit 0: this launch's frames read ONE set of lists, the first frame's; bit 1: so will the frames it places
-    const int share_flags = KBE_SHARED_LISTS ? jp->pad_ : 0;
+    // bit 0: this launch's frames read ONE set of lists, the first frame's; bit 1: so will the frames it places
+    const int share_flags = jp->pad_;
     const bool ahead = NU > 0 && (int) blockIdx.y < n_next;             // uniform: this row has a frame to place
     const int a_units = ahead ? pcp->Np / kCloudBlock : 1;
     const int a_first = blockIdx.x * WAVES + wave, a_step = gridDim.x * WAVES;
@@ -549,25 +555,7 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
             for (int d = 0; d < NU; d++) place_point_end(a_owed[d], (a_first + d * a_step) * kCloudBlock + lane, cand_next);
         }
     };
-#ifndef KBE_LDS_WIDE
-#define KBE_LDS_WIDE 1
-#endif
-    // (KBE_LDS_WIDE: the bin heads and the z keys four entries per store -- 294 ds_write_b128 for the workgroup, one per thread and
-    // a second one for 38 of them, instead of 1 173 single stores in two loops of three trips with their bound tests: a wave's
-    // ~25 vector instructions become ~8, on a launch bound by vector issue)
-    constexpr int HEAD4 = (int) (sizeof(L.head) / 16), ZK4 = KH * KW / 4;
-    static_assert(!KBE_LDS_WIDE || ((KH * KW) % 4 == 0 && offsetof(Lds, head) % 16 == 0 && offsetof(Lds, zpre) % 16 == 0 && sizeof(L.head) % 16 == 0 &&
-                                    HEAD4 <= TILE_THREADS && HEAD4 + ZK4 <= 2 * TILE_THREADS && ZK4 >= TILE_THREADS - HEAD4), "four entries per store");
-    if (KBE_LDS_WIDE) {
-        const int4 nul4 = make_int4(Lds::kNull, Lds::kNull, Lds::kNull, Lds::kNull);
-        const uint4 emp4 = make_uint4(KBE_ZKEY_EMPTY, KBE_ZKEY_EMPTY, KBE_ZKEY_EMPTY, KBE_ZKEY_EMPTY);               // common.py:430
-        if (tid < HEAD4) ((int4*) L.head)[tid] = nul4;
-        else ((uint4*) zk)[tid - HEAD4] = emp4;
-        if (tid < ZK4 - (TILE_THREADS - HEAD4)) ((uint4*) zk)[TILE_THREADS - HEAD4 + tid] = emp4;
-    } else {
-        lds_reset_heads(L, tid);
-        for (int i = tid; i < KH * KW; i += TILE_THREADS) zk[i] = KBE_ZKEY_EMPTY;             // common.py:430
-    }
+    lds_empty_tile(L, tid);
     if (tid == 0) {
         L.nrec = 0;
         F.n_ovf = 0;
@@ -594,10 +582,9 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
     KBE_PROBE(1);
     __syncthreads();
     KBE_PROBE(2);
-    if (KBE_AHEAD_AT == 2) ahead_finish();
     // (only now: every wave of the workgroup has its copy of the count)
     if (tid == 0) {                                     // ready for the next frame's k_place
-        const int sharers = (KBE_SHARED_LISTS && (share_flags & 1)) ? (int) (jp->a_share[job] >> 8) : 1;
+        const int sharers = (share_flags & 1) ? (int) (jp->a_share[job] >> 8) : 1;
         if (sharers > 1) {
             // the list is the sub-group's: the last of its frames' workgroups to get here (each has read the count) zeroes it, and
             // the arrivals' own counter next to it
@@ -675,10 +662,6 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
         }
     };
 
-#ifndef KBE_PLACED_IN_IMAGE
-#define KBE_PLACED_IN_IMAGE 1
-#endif
-    constexpr int KBE_PASS_PLACED = KBE_PLACED_IN_IMAGE ? PASS_IN_IMAGE : 0;
     // ---- the normal path: the points of the listed sub-blocks, their placements and colours requested above (a 96- and a
     // 128-bit load per point).  About a third of the points are near misses that belong to a neighbouring tile: they cost
     // a floor and a range test.  Records beyond REC_CAP (a few tiles in a hundred: two surfaces over one another at a depth
@@ -694,15 +677,14 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
             for (int d = 0; d < DEPTH; d++)
                 if (st0 + d * WAVES < n_steps) {
                     const bool valid = (st0 + d * WAVES) * SUBS_PER_STEP + lane / kCloudSub < n_cand;
-                    if (LAZY) placed_point(PASS_Z | PASS_INSERT | PASS_SPILL | KBE_PASS_PLACED, pl[d].ox, pl[d].oy, pl[d].err, valid, ix[d], 0, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                    else placed_point(PASS_Z | PASS_INSERT | PASS_SPILL | PASS_COLOUR | KBE_PASS_PLACED, pl[d].ox, pl[d].oy, pl[d].err, valid, ix[d], 0, make_float4(cc[d].r, cc[d].g, cc[d].b, cc[d].depth));
+                    if (LAZY) placed_point(PASS_Z | PASS_INSERT | PASS_SPILL | PASS_IN_IMAGE, pl[d].ox, pl[d].oy, pl[d].err, valid, ix[d], 0, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                    else placed_point(PASS_Z | PASS_INSERT | PASS_SPILL | PASS_COLOUR | PASS_IN_IMAGE, pl[d].ox, pl[d].oy, pl[d].err, valid, ix[d], 0, make_float4(cc[d].r, cc[d].g, cc[d].b, cc[d].depth));
                 }
             if (more) fetch_points();
         }
     }
-    if (AHEAD && KBE_AHEAD_AT == 1 && n_next > 0) place_ahead(jp, n_next, tiles_x, tiles_y, wave, lane, NU, (share_flags & 2) != 0);
     KBE_PROBE(3);
-    if (KBE_AHEAD_AT == 3) ahead_finish();
+    ahead_finish();
     __syncthreads();
     KBE_PROBE(4);
     KBE_STOP_AFTER(3);                                          // (dev) + the splat
@@ -715,40 +697,9 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
     TileOut a;
     a.cam.W = W; a.cam.H = H;
     a.zee = ap->zee; a.zee_pre = ap->zee_pre;
-#if defined(KBE_LATE_ARGS) && !KBE_LATE_ARGS
-    a.frame = ap->frame; a.depth = ap->depth; a.mask = ap->mask; a.holes = ap->holes; a.hole_count = ap->hole_count; a.bbox = ap->bbox; a.coarse = ap->coarse;
-    a.render = ap->render; a.existing = ap->existing;
-#endif
 
-    constexpr int ZPER = (KH * KW + TILE_THREADS - 1) / TILE_THREADS;
     constexpr int PER = (CAP + TILE_THREADS - 1) / TILE_THREADS;
-    // keys -> floats in place (a pixel outside the image was never splatted: it reads 1e6 like common.py:430), and the
-    // one decision per tile whether the fp32-only degrid and z test apply
-    auto decode_z = [&]() {
-        bool band = true;
-        if (KBE_LDS_WIDE) {
-            // four keys per thread (the first 153 threads); the band test on the keys, which order as the floats do: smallest and
-            // largest of the four against the keys of the band's ends
-            if (tid < ZK4) {
-                const uint4 k = ((const uint4*) zk)[tid];
-                ((float4*) L.zpre)[tid] = make_float4(zkey_decode(k.x), zkey_decode(k.y), zkey_decode(k.z), zkey_decode(k.w));
-                const uint32_t lo = min(min(k.x, k.y), min(k.z, k.w)), hi = max(max(k.x, k.y), max(k.z, k.w));
-                band = (lo >= zkey_encode(524288.0f)) & (hi <= zkey_encode(1000000.0f));          // degrid_fast_ok of all four
-            }
-        } else {
-#pragma unroll
-        for (int u = 0; u < ZPER; u++) {
-            const int i = tid + u * TILE_THREADS;
-            if (i < KH * KW) {
-                const float z = zkey_decode(zk[i]);
-                L.zpre[i] = z;
-                band = band && degrid_fast_ok(z);
-            }
-        }
-        }
-        const unsigned long long odd = __ballot(!band);
-        if (lane == 0) L.odd_z[tid >> 6] = odd != 0ull;
-    };
+    auto decode_z = [&]() { lds_decode_z(L, tid, lane); };     // (called directly, the kernels' registers are allocated otherwise: DESIGN.md section 4.3)
     auto tile_is_fast = [&]() { return lds_tile_is_fast(L); };
     auto fetch_rgbd = [&](int id) {
         const CloudColour c = colours[id];
@@ -867,9 +818,6 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
         };
         enum { S_ZWIN, S_DEGRID, S_COUNT, S_SCAN, S_RUN, S_DONE };
         int state = S_ZWIN, wb = 0, c0 = 0, done = 0;
-#if defined(KBE_FRAME_STOP) && defined(KBE_FRAME_SKIP_SLOW)      // (dev) what would the launch cost without its slow tiles?
-        state = S_DONE;
-#endif
         fast = false;
         while (state != S_DONE) {                               // uniform
             const int n_win = min(MAXC, n_blocks - wb);
@@ -940,18 +888,16 @@ __device__ __forceinline__ void frame_body(const __attribute__((address_space(4)
 #else
     (void) total;
 #endif
-#if !defined(KBE_LATE_ARGS) || KBE_LATE_ARGS
     asm volatile("" : "+s"(ap) :: "memory");
     a.frame = ap->frame; a.depth = ap->depth; a.mask = ap->mask; a.holes = ap->holes; a.hole_count = ap->hole_count; a.bbox = ap->bbox; a.coarse = ap->coarse;
     a.render = ap->render; a.existing = ap->existing;
-#endif
     tile_epilogue(a, L, acc, tile, x0, y0);
     KBE_PROBE(8);
-    if (AHEAD && KBE_AHEAD_AT != 1) {
+    if (AHEAD) {
         // what the waves did not place up front: further units of the row's frame, further frames (groups that grow)
         asm volatile("" : "+s"(jp) :: "memory");
         const int n_left = jp->n_next;
-        if (n_left > 0) place_ahead(jp, n_left, jp->a[job].tiles_x, jp->a[job].tiles_y, wave, lane, NU, KBE_SHARED_LISTS && (jp->pad_ & 2) != 0);
+        if (n_left > 0) place_ahead(jp, n_left, jp->a[job].tiles_x, jp->a[job].tiles_y, wave, lane, NU, (jp->pad_ & 2) != 0);
     }
     KBE_PROBE(9);
 #if defined(KBE_FRAME_PROBE)
@@ -979,7 +925,7 @@ typedef FrameJobsT<KBE_FRAME_JOBS> FrameJobs;
 // before: 15.7 -> 15.0 us per frame at twelve frames per launch on the bench cloud (1.08 points per pixel: a tile reaches 608
 // records on average, so about half of them send a few records through the spill area and take a second round -- and still);
 // a raw cloud (1.0) 14.4 -> 13.4; caps of 576 / 624 measure 15.4 / 15.1, 636 loses the sixth slot (16.1).  Clouds denser than
-// LEAN_MAX_DENSITY points per pixel keep the roomy build (16.8 M points on 2048^2: 287 us per frame roomy, 295 lean).
+// KBE_LEAN_MAX_DENSITY points per pixel (kbe_fused_plan.h) keep the roomy build (16.8 M points on 2048^2: 287 us per frame roomy, 295 lean).
 #ifndef KBE_FRAME_WAVES
 #define KBE_FRAME_WAVES 5
 #endif
@@ -988,9 +934,6 @@ typedef FrameJobsT<KBE_FRAME_JOBS> FrameJobs;
 #endif
 #ifndef KBE_LEAN_WAVES
 #define KBE_LEAN_WAVES 6
-#endif
-#ifndef KBE_LEAN_MAX_DENSITY
-#define KBE_LEAN_MAX_DENSITY 1.125
 #endif
 constexpr int LEAN_CAP = KBE_LEAN_CAP;
 static_assert(LEAN_CAP >= TILE_THREADS && LEAN_CAP <= REC_CAP, "the lean build holds fewer records than the scratch's tiles are laid out for");
@@ -1025,34 +968,27 @@ __global__ void __launch_bounds__(TILE_THREADS) __attribute__((KBE_FRAME_ATTR)) 
 }  // namespace
 
 namespace kbe {
-// Can the tile launch of n frames make the placements of n_next frames without outliving its own work?  Its waves share them:
-// up to a few units of 64 points per wave (beyond AHEAD_UNITS per wave the launch is k_frame_group_ahead_dense).
-#ifndef KBE_AHEAD_MAX_UNITS
-#define KBE_AHEAD_MAX_UNITS 9
-#endif
-static size_t ahead_units_per_wave(int N, int W, int H, int n, int n_next)        // rounded up
-{
-    const size_t units = (size_t) cloud_layout_base(N).Np / kCloudBlock * (size_t) n_next;
-    const size_t waves = (size_t) ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * (TILE_THREADS / 64) * (size_t) n;
-    return (units + waves - 1) / waves;
-}
+static_assert(KBE_FRAME_JOBS <= SHARE_MAX_FRAMES, "a launch's frames fit a share plan");
+static FusedGrid fused_grid(int Np, int tiles) { return FusedGrid{ Np, tiles, TILE_THREADS / 64, LIST_CAP }; }
 bool fused_can_place_ahead(int N, int W, int H, int n, int n_next)
 {
-    if (n < 1 || n_next < 1) return false;
-    return ahead_units_per_wave(N, W, H, n, n_next) <= (size_t) KBE_AHEAD_MAX_UNITS;
+    return fused_can_place_ahead(fused_grid(cloud_layout_base(N).Np, ((W + TW - 1) / TW) * ((H + TH - 1) / TH)), n, n_next);
 }
 
 // the scatter of n <= KBE_FRAME_JOBS frames of the same packed cloud and frame size: one placement launch (unless the frames are
 // `placed`: the previous tile launch made their placements ahead) and one tile launch, each taking all n frames (frame k: its
 // camera, scratch set, and by `parity` / `turn` the set's bank of placements and lists, hole counter and list total); the tile
-// launch also makes the placements of `next` (n_next frames: the ones the next tile launch on this stream renders)
+// launch also makes the placements of `next` (n_next frames: the ones the next tile launch on this stream renders).  What is
+// decided here -- which frames share lists, which kernel -- is kbe_fused_plan.h's.
 void launch_frames_fused(hipStream_t s, int n, const void* packed, int N, double cloud_focal, const FusedTarget* t, bool placed, int n_next, const FusedTarget* next, int build,
                          double near_depth)
 {
     PlaceJobs pj;
     FrameJobs fj;
     const PackedCloud pc = cloud_open(packed, N, cloud_focal);
-    unsigned n_tiles = 0;
+    const Scratch& sc0 = t[0].sc;
+    const unsigned n_tiles = (unsigned) (sc0.tiles_x * sc0.tiles_y);
+    const FusedGrid grid = fused_grid(pc.Np, (int) n_tiles);
     auto bank_of = [](const FusedTarget& f) { return f.parity == 1 ? 1 : 0; };
     // the set's list totals: frames with placements in front of them alternate between two (read [par], zero [par ^ 1] for the
     // next); in a sequence that places ahead the frame of turn k reads [k % 3], the placement for turn k + 1 counts in
@@ -1065,91 +1001,17 @@ void launch_frames_fused(hipStream_t s, int n, const void* packed, int N, double
         b.bin_flag = (unsigned*) f.sc.hole_count + flag_of(f);
         return b;
     };
-    // (KBE_SHARED_LISTS) which consecutive frames of a group placed ahead share ONE set of candidate lists (FrameJobsT, ShareMode).
-    // The group's cameras must differ in their shifts only.  The frames are cut into sub-groups of s consecutive ones -- the
-    // largest s of 12, 8, 6, 4, 3, 2 for which the nearest point the caller knows of (`near_depth`: objectDepthrange's closest
-    // depth, common.py:88) moves by at most KBE_SHARE_MAX_PX pixels between a sub-group's first and last camera: a sub-block is
-    // listed for the box of its corners under those two cameras, and what the box gains in tiles must stay below what ONE list
-    // for s frames saves (measured).  A camera between the two need not lie on the straight line between
-    // them (a Ken Burns path is a parabola in shift space: shiftX = dU closestDepth(step) / F, common.py:88-100): how far the
-    // sub-groups' cameras stray from their chords goes to the kernel as `dev` and widens the boxes.  Decided from the group's
-    // cameras, the cloud and near_depth alone, so that the launch that places a group and the launch that renders it agree
-    // without being told.
-    struct SharePlan { bool any; float dev[3]; uint8_t lead[KBE_FRAME_JOBS], last[KBE_FRAME_JOBS], size[KBE_FRAME_JOBS]; };
-    auto share_plan = [&](const FusedTarget* g, int m) {
-        SharePlan P = {};
-        for (int k = 0; k < KBE_FRAME_JOBS; k++) { P.lead[k] = P.last[k] = (uint8_t) k; P.size[k] = 1; }
-        if (!KBE_SHARED_LISTS || m < 2 || !(near_depth > 0.0)) return P;
-        // a sub-group's list is longer than a frame's own, and a list beyond LIST_CAP sends its tile down the slow path: only
-        // clouds whose AVERAGE list (1.55 candidates per point of the tile's share, in sub-blocks) leaves a factor of four to
-        // the capacity share (the bench cloud: 54 of 2048; 16.8 M points on 2048^2: 198, its densest tiles 480-500 -- with
-        // lists of 512, until round 5, shared lists reached 515-555 there and eighteen tiles of a video scanned the whole cloud;
-        // with 2048 such a cloud may share: measured the same with and without, 288.7 us per frame)
-        const Scratch& sc = g[0].sc;
-        if (1.55 * (double) pc.Np / kCloudSub / ((double) sc.tiles_x * sc.tiles_y) > LIST_CAP / 4.0) return P;
-        const Camera& c0 = g[0].cam;
-        double big = 1.0;
-        for (int k = 0; k < m; k++) {
-            const Camera& c = g[k].cam;
-            if (c.focal_f != c0.focal_f || c.fb != c0.fb || c.half_w != c0.half_w || c.half_h != c0.half_h || c.W != c0.W || c.H != c0.H ||
-                c.fp32_centre != c0.fp32_centre || !c.has_shift || !c0.fp32_centre) return P;
-            big = fmax(big, fmax(fabs((double) c.sx), fmax(fabs((double) c.sy), fabs((double) c.sz))));
-        }
-        if (big > 100.0) return P;
-        const double F = (double) c0.focal_f, half = 0.5 * (double) (c0.W > c0.H ? c0.W : c0.H);
-        auto spread_px = [&](int a, int b) {            // how far the nearest point moves between cameras a and b, in pixels
-            const Camera& ca = g[a].cam; const Camera& cb = g[b].cam;
-            const double zn = near_depth + fmin((double) ca.sz, (double) cb.sz);
-            if (!(zn > 0.01 * F)) return 1.0e30;
-            return (hypot((double) cb.sx - ca.sx, (double) cb.sy - ca.sy) * F + half * fabs((double) cb.sz - ca.sz)) / zn;
-        };
-        static const int sizes[] = { 12, 8, 6, 4 };         // (sub-groups of 2 or 3 measured slower than lists of their own: 17.4-17.7 against 16.8-17.0 us per frame)
-        int s_sub = 0;
-        for (int q = 0; q < 4 && !s_sub; q++) {
-            const int sz = sizes[q] < m ? sizes[q] : m;
-            if (sz < 4) break;                              // (a group of two or three frames: lists of their own)
-            bool fits = true;
-            for (int a0 = 0; a0 < m && fits; a0 += sz) { const int b0 = (a0 + sz < m ? a0 + sz : m) - 1; fits = b0 == a0 || spread_px(a0, b0) <= (double) KBE_SHARE_MAX_PX; }
-            if (fits) s_sub = sz;
-        }
-        if (!s_sub) return P;
-        // how far the cameras of a sub-group stray from its chord, per axis (+ the shifts' own fp32 rounding)
-        double dev[3] = { 0.0, 0.0, 0.0 };
-        for (int a0 = 0; a0 < m; a0 += s_sub) {
-            const int b0 = (a0 + s_sub < m ? a0 + s_sub : m) - 1;
-            const Camera& ca = g[a0].cam; const Camera& cb = g[b0].cam;
-            const double d[3] = { (double) cb.sx - ca.sx, (double) cb.sy - ca.sy, (double) cb.sz - ca.sz };
-            const double dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-            for (int k = a0 + 1; k < b0; k++) {
-                const Camera& c = g[k].cam;
-                const double e[3] = { (double) c.sx - ca.sx, (double) c.sy - ca.sy, (double) c.sz - ca.sz };
-                double lam = dd > 0.0 ? (e[0] * d[0] + e[1] * d[1] + e[2] * d[2]) / dd : 0.0;
-                lam = lam < 0.0 ? 0.0 : (lam > 1.0 ? 1.0 : lam);
-                for (int q = 0; q < 3; q++) dev[q] = fmax(dev[q], fabs(e[q] - lam * d[q]));
-            }
-        }
-        for (int q = 0; q < 3; q++) dev[q] += 2.0e-6 * big;
-        // (a path that strays from its chords by more than a pixel's worth at the nearest depth is no path to share lists on)
-        const double zn0 = near_depth + fmin((double) c0.sz, (double) g[m - 1].cam.sz);
-        if (!(zn0 > 0.01 * F) || (hypot(dev[0], dev[1]) * F + half * dev[2]) / zn0 > 2.0) return P;
-        for (int a0 = 0; a0 < m; a0 += s_sub) {
-            const int b0 = (a0 + s_sub < m ? a0 + s_sub : m) - 1;
-            for (int k = a0; k <= b0; k++) { P.lead[k] = (uint8_t) a0; P.last[k] = (uint8_t) b0; P.size[k] = (uint8_t) (b0 - a0 + 1); }
-            P.any = P.any || b0 > a0;
-        }
-        for (int q = 0; q < 3; q++) P.dev[q] = (float) (dev[q] * 1.0001);
-        return P;
-    };
-    const SharePlan plan_now = placed ? share_plan(t, n) : share_plan(t, 0), plan_next = share_plan(next, n_next > 0 ? n_next : 0);
-    const bool shared_now = plan_now.any, shared_next = plan_next.any;
-    pj.pc = pc; fj.pc = pc; fj.n_next = n_next; fj.pad_ = (shared_now ? 1 : 0) | (shared_next ? 2 : 0);
+    // the frames this launch renders share lists as the launch that placed them decided (the same plan from the same inputs); frames
+    // placed in front of their own tile launch (k_place) have lists of their own
+    auto plan_of = [&](const FusedTarget* g, int m) { return share_plan([g](int k) -> const Camera& { return g[k].cam; }, m, near_depth, grid); };
+    const SharePlan plan_now = plan_of(t, placed ? n : 0), plan_next = plan_of(next, n_next > 0 ? n_next : 0);
+    pj.pc = pc; fj.pc = pc; fj.n_next = n_next; fj.pad_ = (plan_now.any ? 1 : 0) | (plan_next.any ? 2 : 0);
     for (int q = 0; q < 3; q++) fj.dev[q] = plan_next.dev[q];
     for (int k = 0; k < KBE_FRAME_JOBS; k++) { fj.a_share[k] = plan_now.lead[k] | ((uint32_t) plan_now.size[k] << 8); fj.nx_share[k] = plan_next.lead[k] | ((uint32_t) plan_next.last[k] << 8); }
+    pj.tiles_x = sc0.tiles_x; pj.tiles_y = sc0.tiles_y;
     for (int k = 0; k < KBE_FRAME_JOBS; k++) {
         const FusedTarget& f = t[k < n ? k : 0];
         const Scratch& sc = f.sc;
-        n_tiles = (unsigned) (sc.tiles_x * sc.tiles_y);
-        pj.tiles_x = sc.tiles_x; pj.tiles_y = sc.tiles_y;
         const int par = f.parity == 1 ? 1 : 0;
         pj.a[k] = place_args(f);
         FrameArgs& a = fj.a[k];
@@ -1159,7 +1021,7 @@ void launch_frames_fused(hipStream_t s, int n, const void* packed, int N, double
         a.render = f.render_f32; a.existing = f.existing_f32; a.zee = f.zee_f32; a.zee_pre = f.zee_pre_f32; a.spill = sc.buckets;
         fj.nx[k] = place_args(n_next > 0 ? next[k < n_next ? k : 0] : f);
     }
-    if (shared_now)         // every frame reads the lists its sub-group's first frame's set holds
+    if (plan_now.any)       // every frame reads the lists its sub-group's first frame's set holds
         // (... and still zeroes the list total its OWN set counts in two turns on: a set that joins an unshared or group-first turn
         // later must not count on top of what an earlier such turn left -- totals only grow, and past the budget every tile of the
         // frame scans the whole cloud: ADVICE r4)
@@ -1168,23 +1030,27 @@ void launch_frames_fused(hipStream_t s, int n, const void* packed, int N, double
             if (l != k) { fj.a[k].tile_count = fj.a[l].tile_count; fj.a[k].cand = fj.a[l].cand; fj.a[k].bin_flag = fj.a[l].bin_flag; }
         }
     if (!placed) hipLaunchKernelGGL(k_place, dim3(blocks_for((size_t) pc.Np), n), dim3(256), 0, s, pj);
-    // the lean build (608 records per tile, six workgroups per CU) for clouds of about a point per pixel, the roomy one beyond
-    // (`build`: KBE_STAGE_FUSED_LEAN / _ROOMY force one -- a switch for tests and measurements)
-    const int forced = build;
-    const Scratch& sc0 = t[0].sc;
-    const bool lean = forced ? forced == 1 : (double) pc.Np <= KBE_LEAN_MAX_DENSITY * (double) t[0].cam.W * (double) t[0].cam.H;
-    if (n == 1 && n_next <= 1) {
+    const FusedKernel pick = fused_kernel(grid, t[0].cam.W, t[0].cam.H, n, n_next, build);
+    const bool lean = pick.build == FusedBuild::LEAN;
+    const dim3 tiles(n_tiles, n), threads(TILE_THREADS);
+    switch (pick.shape) {
+    case FusedShape::SINGLE:
+    case FusedShape::SINGLE_AHEAD: {
         FrameJob1 f1;
         f1.pc = pc; f1.n_next = n_next; f1.pad_ = 0; f1.a[0] = fj.a[0]; f1.nx[0] = fj.nx[0];
         f1.dev[0] = f1.dev[1] = f1.dev[2] = 0.0f; f1.a_share[0] = 1u << 8; f1.nx_share[0] = 0;
-        if (n_next) hipLaunchKernelGGL(lean ? k_frame_ahead : k_frame_ahead_roomy, dim3(n_tiles), dim3(TILE_THREADS), 0, s, f1);
-        else hipLaunchKernelGGL(lean ? k_frame : k_frame_roomy, dim3(n_tiles), dim3(TILE_THREADS), 0, s, f1);
-    } else if (n_next) {                                                        // (also: one frame that places several)
-        const bool dense = ahead_units_per_wave(N, sc0.tiles_x * TW, sc0.tiles_y * TH, n, n_next) > (size_t) AHEAD_UNITS + 1;
-        if (dense) hipLaunchKernelGGL(k_frame_group_ahead_dense, dim3(n_tiles, n), dim3(TILE_THREADS), 0, s, fj);
-        else hipLaunchKernelGGL(lean ? k_frame_group_ahead : k_frame_group_ahead_roomy, dim3(n_tiles, n), dim3(TILE_THREADS), 0, s, fj);
+        if (pick.shape == FusedShape::SINGLE_AHEAD) hipLaunchKernelGGL(lean ? k_frame_ahead : k_frame_ahead_roomy, tiles, threads, 0, s, f1);
+        else hipLaunchKernelGGL(lean ? k_frame : k_frame_roomy, tiles, threads, 0, s, f1);
+        break;
     }
-    else hipLaunchKernelGGL(lean ? k_frame_group : k_frame_group_roomy, dim3(n_tiles, n), dim3(TILE_THREADS), 0, s, fj);
+    case FusedShape::GROUP:
+        hipLaunchKernelGGL(lean ? k_frame_group : k_frame_group_roomy, tiles, threads, 0, s, fj);
+        break;
+    case FusedShape::GROUP_AHEAD:
+        if (pick.build == FusedBuild::DENSE) hipLaunchKernelGGL(k_frame_group_ahead_dense, tiles, threads, 0, s, fj);
+        else hipLaunchKernelGGL(lean ? k_frame_group_ahead : k_frame_group_ahead_roomy, tiles, threads, 0, s, fj);
+        break;
+    }
 }
 size_t fused_place_bytes(int N) { return (size_t) cloud_layout_base(N).Np * sizeof(Placement); }
 }  // namespace kbe

@@ -22,7 +22,7 @@ namespace kbe {
 #define KBE_TILE_W 32
 #endif
 #ifndef KBE_TILE_H
-#define KBE_TILE_H 16
+#define KBE_TILE_H 16        // (8 no longer compiles: k_frame writes tile + halo four z keys per store.  That experiment is closed: profiles/r06_tile_height.txt)
 #endif
 #ifndef KBE_TILE_THREADS
 #define KBE_TILE_THREADS 256
@@ -136,7 +136,7 @@ constexpr int KBE_FILL_JOBS = 4;
 #ifndef KBE_FRAME_JOBS_MAX
 #define KBE_FRAME_JOBS_MAX 12        // (12 x sizeof(FrameArgs) = 3.8 KB of kernel arguments: the launch takes 4 KB)
 #endif
-constexpr int KBE_FUSED_MAX_POINTS = 1 << 28;     // the packed cloud's route addresses a point's 16 bytes by a 32-bit byte offset (kbe_fused.hip: KBE_OFFSETS_32)
+constexpr int KBE_FUSED_MAX_POINTS = 1 << 28;     // the packed cloud's route addresses a point's 16 bytes by a 32-bit byte offset (kbe_fused.hip: at_offset32)
 constexpr int KBE_FRAME_JOBS = KBE_FRAME_JOBS_MAX;      // frames a launch of the fused scatter (k_place, k_frame) takes at most
 struct FillTarget {                 // a frame to be filled, on the host
     Scratch sc;
@@ -170,7 +170,7 @@ struct FusedTarget {
 // launch also makes those of `next` (frames that use the other bank of their sets; turn >= 0 everywhere)
 // `build`: 0 = the lean or the roomy build of the tile launch by the cloud's density, 1 = lean, 2 = roomy (KBE_STAGE_FUSED_LEAN / _ROOMY)
 // `near_depth`: the depth of the nearest point the caller knows of (objectDepthrange[0], common.py:88), > 0: consecutive frames placed ahead may share
-// candidate lists (kbe_fused.hip: share_plan); 0: every frame keeps lists of its own
+// candidate lists (kbe_fused_plan.h: share_plan); 0: every frame keeps lists of its own
 void launch_frames_fused(hipStream_t s, int n, const void* packed, int N, double cloud_focal, const FusedTarget* targets, bool placed = false, int n_next = 0,
                          const FusedTarget* next = nullptr, int build = 0, double near_depth = 0.0);
 inline int fused_build_of_stages(int stages) { return (stages & 1024) ? 1 : ((stages & 2048) ? 2 : 0); }
@@ -190,15 +190,10 @@ __device__ __forceinline__ int xcd_tile(int b, int n)
 // band fixed: profiles/r04_scatter_wave_timeline.txt).  Only when the bands are equal (n % 8 == 0): else they are not interchangeable.
 __device__ __forceinline__ int xcd_tile_rot(int b, int n, int job)
 {
-#if defined(KBE_XCD_ROT) && !KBE_XCD_ROT
-    (void) job;
-    return xcd_tile(b, n);
-#else
     if (n & 7) return xcd_tile(b, n);
     // (a launch of fewer than eight frames spreads its frames' bands over the eight: 4 frames -> every second band)
     const int stride = gridDim.y >= 8 ? 1 : 8 / (int) gridDim.y;
     return (((b + job * stride) & 7) * (n >> 3)) + (b >> 3);
-#endif
 }
 
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -216,7 +211,7 @@ template <int CAP> struct TileLdsT {
     float4 rec[CAP + 1];        // ox, oy, dblError, link to the next record of the bin; slot kDummy: see gather
     float4 rgbd[CAP + 1];       // the point's r, g, b, depth, fetched once at insert time
     int head[(BH * BW + 3) & ~3];   // link to the first record of each bin.  A link is the record's BYTE offset, kNull = none (rounded up to whole
-                                // 16-byte words, so that this array and the next can be written four entries at a time: KBE_LDS_WIDE)
+                                // 16-byte words, so that this array and the next can be written four entries at a time: k_frame's set-up)
     float zpre[KH * KW];        // z-buffer before degrid, tile + halo; after the degrid: uint8 staging area + per-wave partials
     float zee[TH * TW];         // degridded z-buffer
     int odd_z[TILE_THREADS / 64];   // per wave: some z of tile + halo is outside [2^19, 1e6] (then: the generic, fp64-capable code); 16-byte aligned: read as one word
@@ -271,9 +266,6 @@ template <class LDS> __device__ __forceinline__ void lds_insert(LDS& L, int idx,
 // the LDS read takes as it is.  The
 // trip count is the longest of the four lists, not their sum.  FAST: every z of the tile is in the band where
 // `zee + 1.0` is exact in fp32 (plus_one_is_exact); otherwise the comparison runs in fp64 where it has to.
-#ifndef KBE_GATHER_PORT2
-#define KBE_GATHER_PORT2 0
-#endif
 template <bool FAST, class Args, class LDS>
 __device__ __forceinline__ void gather(const Args& a, const LDS& L, int tid, int x0, int y0,
                                        PixAcc (&acc)[PIX_PER_THREAD])
@@ -291,38 +283,15 @@ __device__ __forceinline__ void gather(const Args& a, const LDS& L, int tid, int
         // corner k of a point is this pixel  <=>  its north-west corner is (X - (k & 1), Y - (k >> 1)).  That pins
         // floor(ox), floor(oy), so the bilinear weight of common.py:481-484 needs two subtractions and one
         // product: (ex - ox | ox - fx) * (ey - oy | oy - fy) with fx = (float) nwx, ex = (float) (nwx + 1).
-        // KBE_GATHER_PORT2 (FAST tiles): the same arithmetic in instructions a SIMD issues through its SECOND port (DESIGN.md
-        // section 4: plain two-operand fp32 / integer / logic instructions on vector registers co-issue with the first port's,
-        // which the launch is bound by) -- 1: the four channels as separate v_mul_f32 + v_add_f32 instead of packed pairs
-        // (packed fp32 takes the first port); 2: also the z test as a subtraction whose sign masks the weight instead of a
-        // compare and a select.  r.z <= zlimf  <=>  r.z < the float above zlimf  <=>  r.z - that float is negative (both
-        // finite, or r.z = +inf on the dummy record: the difference then is +inf; zlimf = zee + 1 with zee in [2^19, 1e6]).
-        const float zl2 = __int_as_float(__float_as_int(zlimf) + 1);
-        float ar = acc[m].rg.x, ag = acc[m].rg.y, ab = acc[m].bd.x, ad = acc[m].bd.y, aw = acc[m].w;
         auto add = [&](int k, const float4& r, const float4& c) {
             const float wx = (k & 1) ? (r.x - (Xf - 1.0f)) : ((Xf + 1.0f) - r.x);          // k & 1 ? ox - fx : ex - ox
             const float wy = (k >> 1) ? (r.y - (Yf - 1.0f)) : ((Yf + 1.0f) - r.y);
-            float w;
-            if (FAST && KBE_GATHER_PORT2 >= 2) {
-                const float below = r.z - zl2;
-                int sign;
-                w = wx * wy;
-                // (as the instructions: the compiler turns `(x >> 31) & y` back into a compare and a select)
-                asm("v_ashrrev_i32 %0, 31, %1" : "=v"(sign) : "v"(below));
-                asm("v_and_b32 %0, %1, %2" : "=v"(w) : "v"(w), "v"(sign));
-            } else {
-                const bool pass = exact ? (r.z <= zlimf) : ((double) r.z <= zlim);         // :639
-                w = pass ? wx * wy : 0.0f;
-            }
-            if (FAST && KBE_GATHER_PORT2 >= 1) {
-                ar += c.x * w; ag += c.y * w; ab += c.z * w; ad += c.w * w;                 // :641 product rounded, then added
-                aw += w;
-            } else {
-                const f4 cv = *(const f4*) &c;
-                acc[m].rg += cv.xy * w;                                     // :641 product rounded, then added (v_pk_mul_f32, v_pk_add_f32)
-                acc[m].bd += cv.zw * w;
-                acc[m].w += w;                                              // the `ones` channel (:429)
-            }
+            const bool pass = exact ? (r.z <= zlimf) : ((double) r.z <= zlim);             // :639
+            const float w = pass ? wx * wy : 0.0f;
+            const f4 cv = *(const f4*) &c;
+            acc[m].rg += cv.xy * w;                                         // :641 product rounded, then added (v_pk_mul_f32, v_pk_add_f32)
+            acc[m].bd += cv.zw * w;
+            acc[m].w += w;                                                  // the `ones` channel (:429)
         };
         int nx[4];
 #pragma unroll
@@ -340,7 +309,6 @@ __device__ __forceinline__ void gather(const Args& a, const LDS& L, int tid, int
                 nx[k] = __float_as_int(r[k].w);
             }
         } while (min(min(nx[0], nx[1]), min(nx[2], nx[3])) < LDS::kNull);      // some list goes on
-        if (FAST && KBE_GATHER_PORT2 >= 1) { acc[m].rg.x = ar; acc[m].rg.y = ag; acc[m].bd.x = ab; acc[m].bd.y = ad; acc[m].w = aw; }
     }
 }
 
@@ -405,11 +373,7 @@ __device__ __forceinline__ void tile_epilogue(const Args& a, LDS& L, PixAcc (&ac
         // q = a * y, q' = fma(fma(-den, q, a), y, q) per channel -- the correctly rounded a / den (Markstein;
         // tests/markstein_div_check.c) unless an intermediate underflows, i.e. for |a| below ~2^-100, where the
         // last bit may differ (no colour or depth of a real cloud gets there)
-#if defined(KBE_DIV_FAST) && !KBE_DIV_FAST
-        const float y = 1.0f / den;
-#else
         const float y = div_unscaled(1.0f, den);          // den = w + 1e-7 with 0 <= w <= 4 N: in [2^-24, 2^27], nowhere near a rescaling
-#endif
         auto quot = [&](float a_) { const float q = a_ * y; return __builtin_fmaf(__builtin_fmaf(-den, q, a_), y, q); };
         res[m][0] = quot(acc[m].rg.x); res[m][1] = quot(acc[m].rg.y); res[m][2] = quot(acc[m].bd.x); res[m][3] = quot(acc[m].bd.y);
         dms[m] = res[m][3] * (w > 0.0f ? 1.0f : 0.0f);
@@ -475,10 +439,7 @@ __device__ __forceinline__ void tile_epilogue(const Args& a, LDS& L, PixAcc (&ac
     }
     // uint8 rows leave as dwords when the row segment is 4-byte aligned and complete
     const bool dword_rows = (W & 3) == 0 && (TW * 3) % 4 == 0 && x0 + TW <= W;
-#ifndef KBE_EPILOGUE_WIDE
-#define KBE_EPILOGUE_WIDE 1
-#endif
-    if (KBE_EPILOGUE_WIDE && (W & 15) == 0 && (TW * 3) % 16 == 0 && x0 + TW <= W && ((uintptr_t) a.frame & 15) == 0) {
+    if ((W & 15) == 0 && (TW * 3) % 16 == 0 && x0 + TW <= W && ((uintptr_t) a.frame & 15) == 0) {
         // ... as 16-byte words where the row segments are 16-byte aligned (a tile row is 96 bytes: six of them): 96 stores for the
         // tile, by the workgroup's LAST threads (the z decode in front of the degrid is the first threads' work) -- a trip for 96
         // threads instead of two trips with their index arithmetic for all 256

@@ -82,7 +82,7 @@ inline std::vector<int> transfer_group_starts(int n_frames, int G, bool fast_ram
     return starts;
 }
 
-// can_place_ahead(n, n_next): may a launch of n frames make the placements of n_next more (kbe_fused.hip: fused_can_place_ahead)
+// can_place_ahead(n, n_next): may a launch of n frames make the placements of n_next more (kbe_fused_plan.h: fused_can_place_ahead)
 template <class CanPlaceAhead>
 VideoPlan plan_video(const VideoPlanIn& in, CanPlaceAhead can_place_ahead)
 {
@@ -104,7 +104,7 @@ VideoPlan plan_video(const VideoPlanIn& in, CanPlaceAhead can_place_ahead)
     switch (in.dest) {
     case VideoDest::HBM:
         // a chunk of per * lanes CONSECUTIVE frames at a time, lane l taking frames base + l * per .. base + l * per + per - 1 of it
-        // (consecutive cameras share candidate lists, kbe_fused.hip: share_plan; until round 5 lane l took frames l, l + lanes, ...:
+        // (consecutive cameras share candidate lists, kbe_fused_plan.h: share_plan; until round 5 lane l took frames l, l + lanes, ...:
         // cameras `lanes` steps apart in every launch: 40.4 k frames/s at 75 frames, 40.8 k consecutive).  The last, partial chunk fills the
         // lanes one after the other, `per` frames each.  (ADVICE r5 proposed to deal it evenly, ceil(remaining / lanes) frames per lane, so that every lane
         // has work: measured in round 6 -- tools/batches/gpu_r06_tail.sh, frames/s left in HBM, lane by lane / evenly: 6 frames 26.5 /

@@ -79,7 +79,7 @@ def shard_indices(n, rank, world_size, shape=None):
     of a Ken Burns path costs ~7-14 % more than one in its middle, and the video ends with its slowest rank.
     'block': a contiguous run of n / world_size frames (the first n % world_size ranks one more) -- consecutive cameras, which
     the renderer's launch groups like (the frames of a launch share candidate lists built for the box between a sub-group's
-    first and last camera: kbe_fused.hip share_plan) -- but the ranks holding the path's ends set the pace.
+    first and last camera: kbe_fused_plan.h share_plan) -- but the ranks holding the path's ends set the pace.
     'dealt<k>' (e.g. 'dealt2'): runs of k consecutive frames dealt to the ranks in turn.
     Measured as an 8-way share of a 128- and a 75-frame 1024^2 video on one GPU (tools/shard_shapes.py; every rank of a node
     has its own GPU and link, so a share rendered alone is what that rank would do), the video at its slowest rank's pace,

@@ -853,10 +853,11 @@ def test_cloud_of_nine_points_per_pixel_on_all_three_routes_against_the_oracle(K
 @pytest.mark.parametrize('steps', [20, 75, 400])
 def test_video_on_a_ken_burns_path_with_shared_lists_equals_the_video_with_lists_per_frame(K, monkeypatch, steps):
     """The candidate lists of consecutive frames are shared in sub-groups whose size follows the nearest point's motion between a
-    sub-group's first and last camera (kbe_fused.hip share_plan; near_depth = objectDepthrange[0]): on the product's own camera path --
+    sub-group's first and last camera (kbe_fused_plan.h share_plan; near_depth = objectDepthrange[0]): on the product's own camera path --
     a parabola in shift space -- with 20 steps (7 px per step at 512^2 scaled: lists per frame), 75 (sub-groups) and 400 (whole
     launches share), one lane so that launches of twelve follow one another: the same frames as with KBE_SHARE_LISTS=0 (near_depth 0:
-    every frame its own lists), and as the oracle's for a sample of them."""
+    every frame its own lists), and as the oracle's for a sample of them.  (That the plan does share on such a path, and in which
+    sub-groups, is asserted without a GPU: tests/test_fused_plan.py::test_share_plan_fires_on_a_ken_burns_path.)"""
     from ken_burns_effect_amd import common
     monkeypatch.setenv('KBE_LANES', '1')
     monkeypatch.setenv('KBE_FILL_GROUP', '12')

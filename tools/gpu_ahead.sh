@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: tools/ahead_time.py for the shipped library and for variant builds (quoted sets of extra hipcc flags).
-#   gpurun -- 'bash tools/gpu_ahead.sh "-DKBE_AHEAD_AT=1"'
+#   bash tools/gpu_ahead.sh "-DKBE_AHEAD_UNITS=2"
 export HSA_ENABLE_IPC_MODE_LEGACY=0 MIOPEN_FIND_MODE=FAST
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The tile counters of a delivered video (dev aid): a -DKBE_FRAME_STATS [-DKBE_SHARED_LISTS=1] build renders FRAMES frames of a
-cloud to pinned host memory and reports list entries, candidates, wide sub-blocks and slow tiles per frame."""
+"""The tile counters of a delivered video (dev aid): a -DKBE_FRAME_STATS build renders FRAMES frames of a cloud to pinned host
+memory and reports list entries, candidates, wide sub-blocks and slow tiles per frame (SHARE=0: with KBE_SHARE_LISTS=0, lists per frame)."""
 import ctypes
 import os
 import subprocess
@@ -9,7 +9,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 so = '/tmp/libkbe_share_stats.so'
-flags = '-DKBE_FRAME_STATS' + (' -DKBE_SHARED_LISTS=1' if os.environ.get('SHARE', '1') == '1' else '')
+flags = '-DKBE_FRAME_STATS'
+if os.environ.get('SHARE', '1') != '1':
+    os.environ['KBE_SHARE_LISTS'] = '0'
 subprocess.check_call(['make', '-s', '-B', '-C', os.path.join(ROOT, 'ken-burns-effect_amd', 'csrc'), 'EXTRA=' + flags, 'OUT=' + so])
 import torch  # noqa: E402
 
@@ -33,5 +35,5 @@ for rep in range(2):
     torch.cuda.synchronize()
     K.lib.kbe_debug_frame_stats(out, 1)
     t = max(1, out[0])
-    print('%s: tiles %d: list entries %.1f, candidate sub-blocks %.1f, points in z reach %.0f, records %.0f per tile; wide sub-blocks %d; tiles on the slow path %d, with a second round %d'
-          % (flags, out[0], out[1] / t, out[2] / t, out[3] / t, out[4] / t, out[7], out[5], out[6]))
+    print('%s, SHARE=%s: tiles %d: list entries %.1f, candidate sub-blocks %.1f, points in z reach %.0f, records %.0f per tile; wide sub-blocks %d; tiles on the slow path %d, with a second round %d'
+          % (flags, os.environ.get('SHARE', '1'), out[0], out[1] / t, out[2] / t, out[3] / t, out[4] / t, out[7], out[5], out[6]))
