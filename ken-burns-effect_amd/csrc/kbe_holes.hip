@@ -1,6 +1,7 @@
 // kbe_holes.hip -- fill_disocclusion (common.py:833-937) of a frame from its hole list: the three schedules of k_fill_holes /
 // k_fill_tables (results identical, byte for byte) and the per-frame tables of the third (k_hole_dist).  DESIGN.md section 4.
 #include "kbe_tiles.h"
+#include "kbe_fill_walk.h"
 
 using namespace kbe;
 
@@ -12,13 +13,21 @@ namespace {
 // "strictly shorter, first direction wins" reduction picks the same source pixel)
 // ---------------------------------------------------------------------------------------
 
+// the hole px takes the pixel of the farther (background) one of the two ends (ax, ay), (bx, by) of its winning direction (:904)
+__device__ __forceinline__ void fill_from(int px, int ax, int ay, int bx, int by, const float* __restrict__ depth, int W, int H,
+                                          uint8_t* __restrict__ frame, float* __restrict__ render)
+{
+    int sx = ax, sy = ay;
+    if (depth[(size_t) ay * W + ax] < depth[(size_t) by * W + bx]) { sx = bx; sy = by; }
+    const size_t s = (size_t) sy * W + sx, o = (size_t) px, HW = (size_t) W * H;
+    frame[o * 3] = frame[s * 3]; frame[o * 3 + 1] = frame[s * 3 + 1]; frame[o * 3 + 2] = frame[s * 3 + 2];
+    if (render) for (int c = 0; c < 4; c++) render[c * HW + o] = render[c * HW + s];
+}
+
 #ifndef KBE_FILL_SERIAL_BATCH
 #define KBE_FILL_SERIAL_BATCH 8
 #endif
 constexpr int COARSE_WORDS = 2048;     // 8 x 8 blocks of images up to 2048 x 2048 (larger: the walks do not skip)
-#ifndef KBE_FILL_SERIAL_MIN
-#define KBE_FILL_SERIAL_MIN 49152       // holes per frame from which one lane per hole beats one half-wave per hole
-#endif
 
 // Frames with very many holes (dolly: no inpainting, common.py:217; hundreds of thousands of holes in wide
 // disocclusion bands): ONE LANE PER HOLE, the 16 directions in the reference's order, both ends of a direction
@@ -158,11 +167,7 @@ __device__ __forceinline__ void fill_hole_serial(int px, const float* __restrict
         if (best > dist) { best = dist; best_s = sq; sax = ax; say = ay; sbx = bx; sby = by; }     // :900
     }
     if (sax < 0) return;                                        // unfillable: keeps the rendered value (:913-919)
-    int sx = sax, sy = say;
-    if (depth[(size_t) say * W + sax] < depth[(size_t) sby * W + sbx]) { sx = sbx; sy = sby; }     // :904 the farther (background) end
-    const size_t s = (size_t) sy * W + sx, o = (size_t) px, HW = (size_t) W * H;
-    frame[o * 3] = frame[s * 3]; frame[o * 3 + 1] = frame[s * 3 + 1]; frame[o * 3 + 2] = frame[s * 3 + 2];
-    if (render) for (int c = 0; c < 4; c++) render[c * HW + o] = render[c * HW + s];
+    fill_from(px, sax, say, sbx, sby, depth, W, H, frame, render);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -186,112 +191,17 @@ __device__ __forceinline__ void fill_hole_serial(int px, const float* __restrict
 #ifndef KBE_DIST_CAP_BLOCKS
 #define KBE_DIST_CAP_BLOCKS 15
 #endif
-constexpr int DT_W = 64, DT_H = 32;                 // interior of one workgroup: 2 words x 32 rows
 constexpr int DT_WORDS = 4;
 static_assert(DT_W == 64, "the halo is one 32-pixel word on each side");
 
-// Strip tables.  A ray of direction u through a hole p stays within 0.75 pixels of the line through p (positions are
-// rounded per axis; the fp32 sums drift by < 0.03 over 1000 steps), so the only valid pixels it can ever meet lie in the
-// strip of lines c in [b - 1, b + 2), b = floor(c(p)), c(q) = n . q the coordinate across the direction.  Per direction
-// and b, (lo, hi) bound the coordinate t(q) = u . q along the direction over every valid pixel of that strip -- or rather
-// over exactly those (build_strips: the tiles' boxes first, then the bitmask's rows at either end).  The end walking towards -u meets nothing once lo > t + 1, the end towards +u once hi < t - 1: the
-// direction is skipped (common.py:880-885, 891-896) without walking to the image border.  A zoomed-out frame is mostly
-// border around a convex patch of valid pixels; outside a convex patch NO direction has valid pixels on both sides.
-// Measured on the last frame of the dolly bench (266 k holes inside the box of valid pixels): 1.7 of a hole's 16 directions
-// complete, 4.5 pass this test; pixel steps per hole 6811 -> 560 (tools/strip_proto.c, against brute-force walks: no
-// direction that completes is ever skipped).
-constexpr float STRIP_MARGIN = 1.0f;
-__host__ __device__ __forceinline__ int strip_bins(int W, int H) { return W + H + 8; }
-// c(q) = -uy x + ux y over the image starts at -(max(0, uy W) + max(0, -ux H)); + 2 keeps b - 1 non-negative
-__device__ __forceinline__ int strip_offset(float ux, float uy, int W, int H)
-{
-    return (int) ceilf(fmaxf(0.0f, uy * (float) W) + fmaxf(0.0f, -ux * (float) H)) + 2;
-}
-
+// a workgroup's 256 bins of one direction's strip table, from first_bin on
 __device__ void build_strips(const int4* __restrict__ bbox, const uint32_t* __restrict__ mask, int tiles_x, int tiles_y, int W, int H, float ux, float uy,
                              int first_bin, float2* __restrict__ out)
 {
     const int b = first_bin + (int) threadIdx.x;
     if (b >= strip_bins(W, H)) return;
-    const float c0 = (float) (b - strip_offset(ux, uy, W, H)) - STRIP_MARGIN, c1 = c0 + 1.0f + 2.0f * STRIP_MARGIN;
-    // Per tile row (tile column for a flat direction) the one to three tiles under the strip, each with the box of its own valid pixels
-    // (the tile launch's bbox table), the strip clipped to the box; then the tile whose box reaches farthest towards either end of the
-    // strip is looked at ROW BY ROW in the validity bitmask: its valid pixels of the strip give that end's bound, unless another tile's
-    // box reaches farther than they do (then that box's reach does: still a superset).  Until round 5: the x-extent of each whole tile
-    // ROW (the y-extent of each tile column) -- 4.46 of a late dolly frame's 16 directions per hole passed the test where 1.73
-    // complete; the tiles' own boxes alone: 2.47; with the one tile looked at: 2.01; every tile looked at until nothing can improve
-    // (exact): 1.91 -- but that walk's chain of dependent loads made k_hole_dist slower than the fill gained (tools/strip_proto.c on
-    // the oracle's masks, the restatement of this function).  The directions that pass without completing are the expensive ones: they
-    // walk to the end of their strip.
-    const bool steep = fabsf(uy) >= fabsf(ux);                  // the line crosses every row once: walk the tile rows
-    const int n = steep ? tiles_y : tiles_x, m = steep ? tiles_x : tiles_y;
-    const float ua = steep ? ux : uy, ub = steep ? uy : ux;     // a = the coordinate along a row (column), b = across
-    const float inv = 1.0f / ub;
-    const int sa = steep ? TW : TH, sb = steep ? TH : TW;
-    const int wpr = (W + 31) >> 5;
-    const bool rows_cross = fabsf(uy) >= 1.0e-6f;               // else: a horizontal direction, a strip is whole rows
-    const float inv_uy = rows_cross ? 1.0f / uy : 0.0f;
-    static_assert(TW == 32 && TH <= 16, "a tile row is one word of the validity bitmask, a tile at most sixteen of them");
-    // the strip's extent along a over the rows (columns) b0 .. b1 -- steep: c = -uy x + ux y => x = (ux y - c) / uy; flat: y = (c + uy x) / ux
-    const auto along = [&](float b0, float b1, float& a0, float& a1) {
-        const float v0 = steep ? (ua * b0 - c0) * inv : (c0 + ua * b0) * inv, v1 = steep ? (ua * b0 - c1) * inv : (c1 + ua * b0) * inv;
-        const float v2 = steep ? (ua * b1 - c0) * inv : (c0 + ua * b1) * inv, v3 = steep ? (ua * b1 - c1) * inv : (c1 + ua * b1) * inv;
-        a0 = fminf(fminf(v0, v1), fminf(v2, v3)) - 0.01f; a1 = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)) + 0.01f;
-    };
-    float lo1 = INFINITY, lo2 = INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;        // the farthest and the second farthest reach of a box, either end
-    int lo_tile = -1, hi_tile = -1;
-    for (int i = 0; i < n; i++) {
-        float a0, a1;
-        along((float) (i * sb), (float) (i * sb + sb - 1), a0, a1);
-        const int j0 = max((int) floorf(a0 / (float) sa), 0), j1 = min((int) floorf(a1 / (float) sa), m - 1);
-        for (int j = j0; j <= j1; j++) {
-            const int tile = steep ? i * tiles_x + j : j * tiles_x + i;
-            const int4 bb = bbox[tile];
-            if (bb.z < bb.x) continue;                          // a tile without a valid pixel
-            const float q0 = (float) (steep ? bb.y : bb.x), q1 = (float) (steep ? bb.w : bb.z);        // the box across ...
-            float p0, p1;
-            along(q0, q1, p0, p1);
-            p0 = fmaxf(p0, (float) (steep ? bb.x : bb.y)); p1 = fminf(p1, (float) (steep ? bb.z : bb.w));     // ... and along
-            if (p0 > p1) continue;
-            // t = ux x + uy y = ua a + ub b over [p0, p1] x [q0, q1]
-            const float t0 = ua * p0 + ub * q0, t1 = ua * p0 + ub * q1, t2 = ua * p1 + ub * q0, t3 = ua * p1 + ub * q1;
-            const float tmin = fminf(fminf(t0, t1), fminf(t2, t3)), tmax = fmaxf(fmaxf(t0, t1), fmaxf(t2, t3));
-            if (tmin < lo1) { lo2 = lo1; lo1 = tmin; lo_tile = tile; } else lo2 = fminf(lo2, tmin);
-            if (tmax > hi1) { hi2 = hi1; hi1 = tmax; hi_tile = tile; } else hi2 = fmaxf(hi2, tmax);
-        }
-    }
-    // the valid pixels of the strip in one tile, row by row in the bitmask (the sixteen words requested together): the smallest
-    // (`low`) or the largest t among them; none: +inf / -inf
-    const auto in_tile = [&](int tile, bool low) -> float {
-        float best = low ? INFINITY : -INFINITY;
-        if (tile < 0) return best;
-        const int4 bb = bbox[tile];
-        const int ty = tile / tiles_x, tx = tile - ty * tiles_x, x0 = tx * TW;
-        uint32_t words[TH];
-#pragma unroll
-        for (int r = 0; r < TH; r++) words[r] = mask[(size_t) min(bb.y + r, bb.w) * wpr + tx];
-#pragma unroll
-        for (int r = 0; r < TH; r++) {
-            const int y = bb.y + r;
-            if (y > bb.w) continue;
-            float xa = -1.0e9f, xb = 1.0e9f;
-            if (rows_cross) {
-                const float e0 = (ux * (float) y - c0) * inv_uy, e1 = (ux * (float) y - c1) * inv_uy;
-                xa = fminf(e0, e1) - 0.01f; xb = fmaxf(e0, e1) + 0.01f;
-            } else {
-                const float c = ux * (float) y;
-                if (c < c0 - 0.01f || c > c1 + 0.01f) continue;
-            }
-            const int xl = (int) ceilf(fmaxf(xa, (float) bb.x)), xr = (int) floorf(fminf(xb, (float) bb.z));
-            if (xl > xr) continue;
-            const uint32_t w = words[r] & (0xFFFFFFFFu << (xl - x0)) & (0xFFFFFFFFu >> (31 - (xr - x0)));
-            if (!w) continue;
-            const float ta = ux * (float) (x0 + __builtin_ctz(w)) + uy * (float) y, tb = ux * (float) (x0 + 31 - __builtin_clz(w)) + uy * (float) y;
-            best = low ? fminf(best, fminf(ta, tb)) : fmaxf(best, fmaxf(ta, tb));
-        }
-        return best;
-    };
-    const float lo = fminf(in_tile(lo_tile, true), lo2), hi = fmaxf(in_tile(hi_tile, false), hi2);
+    float lo, hi;
+    strip_bounds<TW, TH>(b, bbox, mask, tiles_x, tiles_y, W, H, ux, uy, lo, hi);
     out[b] = make_float2(lo, hi);
 }
 
@@ -404,54 +314,6 @@ __device__ __forceinline__ void hole_dist_body(const uint32_t* __restrict__ mask
                      (int) blockIdx.x, (int) blockIdx.y, W, H, W, dist);
 }
 
-// the contest's key holds an end's step count in 14 bits: a ray takes at most max(W, H) / 0.707 steps (larger frames
-// fill with the other schedules)
-inline bool fill_tables_fit(int W, int H) { return W <= 11000 && H <= 11000; }
-
-// the extents the strip tables are built from: up to STRIP_TILES tile rows / columns
-inline bool strips_fit(const Scratch& sc) { return sc.tiles_x <= STRIP_TILES && sc.tiles_y <= STRIP_TILES; }
-
-// m repeated fp32 additions a := a - u (or + u), exactly, in a few steps.  While a stays in one binade [2^e, 2^(e+1))
-// every value of the chain is a multiple of q = 2^(e-23), and each rounded sum moves a by the SAME amount R = u rounded to
-// a multiple of q: the exact sum lies between two neighbours of a's grid, and which one is nearer does not depend on a --
-// unless u sits exactly half-way between two multiples of q (a tie: round-to-even looks at a).  j such sums are a -/+ j R,
-// computed on the integer mantissa.  j is cut so that the chain, and one step beyond it on either side, stays inside the
-// binade (no sum is rounded on a finer or a coarser grid); across a binade boundary, for ties, below 1 and for the last
-// two steps the sums are added one at a time.  (tools/advance_check.c: against step-by-step sums, 24 M cases.)
-// `limit`: positions below -1 or above limit + 1 are outside the image for good (the ray is monotone), where the value
-// no longer matters: the direction is skipped (common.py:880-885).
-__device__ __forceinline__ float advance_exact(float a, float u, int m, bool subtract, float limit)
-{
-    if (u == 0.0f) return a;
-    while (m > 0) {
-        const uint32_t bits = __float_as_uint(a);
-        const int e = (int) (bits >> 23) - 127;
-        if (m >= 3 && a >= 1.0f && e <= 23) {
-            const float sc = ldexpf(u, 23 - e);                 // u / q, exact
-            const float r = rintf(sc);
-            if (fabsf(sc - r) != 0.5f) {
-                const int step = (int) r, mag = abs(step);
-                const int A = (int) ((bits & 0x7FFFFFu) | 0x800000u);       // a / q in [2^23, 2^24)
-                const bool down = subtract ? step > 0 : step < 0;
-                const int room_down = A - (1 << 23) - mag, room_up = (1 << 24) - 1 - mag - A;
-                const int room = down ? room_down : room_up, other = down ? room_up : room_down;
-                int j = (room > 0 && other >= 0 && mag > 0) ? (int) ((float) room / (float) mag) - 1 : 0;     // <= room / mag for sure
-                j = min(j, m);
-                if (j >= 1) {
-                    const int end = A + j * (down ? -mag : mag);
-                    a = __uint_as_float((bits & 0xFF800000u) | ((uint32_t) end & 0x7FFFFFu));
-                    m -= j;
-                    continue;
-                }
-            }
-        }
-        a = subtract ? a - u : a + u;
-        m--;
-        if (a < -1.0f || a > limit) break;
-    }
-    return a;
-}
-
 #if defined(KBE_FRAME_STATS)     // dev build only (tools/fill_stats.py)
 __device__ unsigned long long g_fill_stats[8];      // holes walked, directions walked, fine look-ups, coarse look-ups, -, directions cut by the bound, directions skipped, skipped before a step
 #define KBE_FILL_STAT(i, v) atomicAdd(&g_fill_stats[i], (unsigned long long) (v))
@@ -463,75 +325,6 @@ __device__ unsigned long long g_fill_hist[16];       // ray ends by the loop ite
 #define KBE_FILL_RAY_DONE(iters, steps) ((void) 0)
 #endif
 
-// One coordinate of a ray end while it walks.  Fast mode (e >= 0): the coordinate is A 2^(e-23) with A in [2^23, 2^24),
-// and one fp32 addition of -/+ u moves A by `step` (advance_exact's argument, kept as state): m additions are one
-// multiply-add and one range test, the pixel a shift.  Invariant of the fast mode: A, and one step to either side of it,
-// inside the binade.  Slow mode (e < 0; A holds the float's bits): below 32, next to a binade boundary, or a tie --
-// single additions until the fast mode can be entered again.
-struct Axis { int A, step, e; };
-
-__device__ __forceinline__ bool axis_interior(int A, int mag) { return (unsigned) (A - (1 << 23) - mag) < (unsigned) ((1 << 23) - 2 * mag); }
-
-__device__ __forceinline__ Axis axis_enter(float f, float u, bool subtract)
-{
-    const uint32_t bits = __float_as_uint(f);
-    const int e = (int) (bits >> 23) - 127;
-    if (f >= 32.0f && e <= 22) {                                // |step| <= 2^18: m * step cannot overflow, 2 |step| < 2^23
-        const float sc = ldexpf(u, 23 - e);                     // u / q, exact
-        const float r = rintf(sc);
-        const int step = subtract ? -(int) r : (int) r;
-        const int A = (int) ((bits & 0x7FFFFFu) | 0x800000u);
-        if (fabsf(sc - r) != 0.5f && axis_interior(A, abs(step))) return Axis{ A, step, e };
-    }
-    return Axis{ (int) bits, 0, -1 };
-}
-
-__device__ __forceinline__ float axis_value(const Axis& ax)
-{
-    return ax.e >= 0 ? __uint_as_float(((uint32_t) (ax.e + 127) << 23) | ((uint32_t) ax.A & 0x7FFFFFu)) : __int_as_float(ax.A);
-}
-
-__device__ __forceinline__ int axis_pixel(const Axis& ax)      // (int) roundf(value): positive values round half up
-{
-    if (ax.e >= 0) { const int sh = 23 - ax.e; return (ax.A + (1 << (sh - 1))) >> sh; }
-    return (int) roundf(__int_as_float(ax.A));
-}
-
-// r pending additions, all at once if they end inside the binade (and the invariant holds at the end: everything in between
-// lies between two interior values)
-__device__ __forceinline__ void axis_jump(Axis& ax, int& r)
-{
-    if (ax.e >= 0) {
-        const int end = ax.A + r * ax.step;
-        if (axis_interior(end, abs(ax.step))) { ax.A = end; r = 0; }
-    }
-}
-
-// ... otherwise, typically in front of a binade boundary: as many as fit in front of it at once, four single additions in
-// fp32 (that is across), whatever mode the value is in then, and the rest at once if they fit now.  What is left stays
-// pending: the lane comes back in the next iteration of its loop.  Kept short on purpose -- in a wave of 64 some lane
-// is here in almost every iteration (9 % of the advances: an image has a binade boundary in its middle), and the wave
-// pays for its longest lane (a loop to completion here: 3/4 of the kernel's time).
-__device__ __forceinline__ void axis_catch_up(Axis& ax, int& r, float u, bool subtract, float limit)
-{
-    if (u == 0.0f) { r = 0; return; }                           // a + 0 = a
-    if (ax.e >= 0) {
-        const int mag = max(1, abs(ax.step));
-        const int room = ax.step < 0 ? ax.A - (1 << 23) - mag : (1 << 24) - 1 - mag - ax.A;
-        const int j = min(r, (int) ((float) room * __builtin_amdgcn_rcpf((float) mag)) - 1);
-        if (j >= 1 && axis_interior(ax.A + j * ax.step, mag)) { ax.A += j * ax.step; r -= j; }      // the test is what counts, j only a guess
-    }
-    float f = axis_value(ax);
-#pragma unroll
-    for (int i = 0; i < 4; i++) if (r > 0) { f = subtract ? f - u : f + u; r--; }       // :876-877 / :887-888
-    if (f < -1.0f || f > limit) r = 0;                          // outside the image for good: the value no longer matters
-    ax = axis_enter(f, u, subtract);
-    if (r > 0) axis_jump(ax, r);
-}
-
-#ifndef KBE_FILL_TABLES_BLOCKS
-#define KBE_FILL_TABLES_BLOCKS 768      // workgroups of k_fill_tables per frame (3 per CU; with four frames per launch and four lanes: 96.5 us per dolly frame, 2048: 99.5)
-#endif
 #ifndef KBE_FILL_BURST
 #define KBE_FILL_BURST 4                // steps a creeping ray takes together (8: 102 us per dolly frame, 4: 99, with four frames per launch) ...
 #endif
@@ -541,11 +334,6 @@ __device__ __forceinline__ void axis_catch_up(Axis& ax, int& r, float u, bool su
 #ifndef KBE_FILL_REFILL_MIN
 #define KBE_FILL_REFILL_MIN 16          // lanes of a wave that must be waiting before new work is fetched
 #endif
-#ifndef KBE_FILL_FINE_BELOW
-#define KBE_FILL_FINE_BELOW 2           // coarse distances below this ask the fine table as well (longer jumps, one more load)
-#endif
-constexpr unsigned long long FILL_NO_ENTRY = ~0ull;
-constexpr int FILL_MAX_STEPS = (1 << 14) - 1;
 enum { END_IDLE = 0, END_WALK = 1, END_HIT = 2, END_DEAD = 3 };
 
 __device__ __forceinline__ int swap_with_neighbour(int v)       // lanes 2i and 2i + 1 exchange v (all lanes active)
@@ -668,14 +456,14 @@ __device__ __forceinline__ void fill_tables_body(const int* __restrict__ holes, 
 #pragma unroll
                 for (int d = 0; d < 16; d++) {
                     const float ddx = s_dir[0][d], ddy = s_dir[1][d];
-                    const float c = ddx * (float) y - ddy * (float) x, t = ddx * (float) x + ddy * (float) y;
-                    const float2 lh = strips[(size_t) d * bins + ((int) floorf(c) + s_off[d])];
-                    if (!(lh.x > t + STRIP_MARGIN || lh.y < t - STRIP_MARGIN)) pass |= 1u << d;     // valid pixels on both sides
+                    const float c = strip_across(ddx, ddy, x, y), t = strip_along(ddx, ddy, x, y);
+                    const float2 lh = strips[(size_t) d * bins + (strip_line(c) + s_off[d])];
+                    if (!(lh.x > t + STRIP_MARGIN || lh.y < t - STRIP_MARGIN)) pass |= 1u << d;     // strip_skip, written out: DESIGN.md section 4
                 }
             }
             if (pass) {
                 const int c_here = block_distance((y >> 3) * cw + (x >> 3));
-                s_m0[tid] = (uint8_t) (c_here >= 2 ? 8 * (c_here - 1) : max(1, (int) dist[(uint32_t) px] - 1));
+                s_m0[tid] = (uint8_t) (c_here >= 2 ? first_jump_from_blocks(c_here) : first_jump_from_pixels(dist[(uint32_t) px]));
             }
         }
         s_px[tid] = px;
@@ -715,8 +503,7 @@ __device__ __forceinline__ void fill_tables_body(const int* __restrict__ holes, 
                                 const int ka = is_b ? pk : k, kb = is_b ? k : pk;
                                 const float dd = sqrtf(ssq);                                // :898
                                 if (!is_b && 1000000.0f > dd && ka <= FILL_MAX_STEPS && kb <= FILL_MAX_STEPS)      // :854, :900
-                                    atomicMin(&s_key[slot], ((unsigned long long) __float_as_uint(dd) << 32) | ((unsigned long long) d << 28) |
-                                                            ((unsigned long long) ka << 14) | (unsigned long long) kb);
+                                    atomicMin(&s_key[slot], fill_key_pack(dd, d, ka, kb));
                                 st = END_IDLE;
                             } else if (ssq > best * best * 1.000001f) {                     // NaN: never true
                                 KBE_FILL_STAT(5, is_b ? 0 : 1);
@@ -747,16 +534,13 @@ __device__ __forceinline__ void fill_tables_body(const int* __restrict__ holes, 
                                 const int ci = (iy >> 3) * cw + (ix >> 3);
                                 const int c = block_distance(ci);
                                 KBE_FILL_STAT(3, 1);
-                                // With the nearest valid pixel D away (Chebyshev) from this one, the pixel j steps
-                                // on is at most j max(|ux|, |uy|) + 1 away from this one (the steps; the rounding of
-                                // both positions; < 0.03 of drift): a hole for sure while j umax + 1.03 < D.  The first
-                                // position to look at is step ceil((D - 1.03) / umax).
-                                if (c >= KBE_FILL_FINE_BELOW) m = (int) ceilf((float) (8 * (c - 1)) * inv_umax - 0.03f);   // D >= 8 (c - 1) + 1
+                                // how far the distance tables let the ray jump: kbe_fill_walk.h
+                                if (c >= KBE_FILL_FINE_BELOW) m = jump_from_blocks(c, inv_umax);
                                 else {
                                     const int dn = dist[(uint32_t) iy * (uint32_t) W + (uint32_t) ix];
                                     KBE_FILL_STAT(2, 1);
                                     if (dn == 0) st = END_HIT;          // depth > 0 (:882 / :893)
-                                    else m = max(c >= 2 ? (int) ceilf((float) (8 * (c - 1)) * inv_umax - 0.03f) : 1, (int) ceilf(((float) dn - 1.03f) * inv_umax));
+                                    else m = max(c >= 2 ? jump_from_blocks(c, inv_umax) : 1, jump_from_pixels(dn, inv_umax));
                                 }
                             }
                             rx = ry = m;
@@ -799,7 +583,7 @@ __device__ __forceinline__ void fill_tables_body(const int* __restrict__ holes, 
                     ix = bpx[B - 1]; iy = bpy[B - 1];
                     X = axis_enter(fx, ux, !is_b);
                     Y = axis_enter(fy, uy, !is_b);
-                    const int m = max(1, (int) ceilf(((float) bdn[B - 1] - 1.03f) * inv_umax));
+                    const int m = max(1, jump_from_pixels(bdn[B - 1], inv_umax));
                     rx = ry = m;
                     k += B + m;
                 }
@@ -838,19 +622,12 @@ __device__ __forceinline__ void fill_tables_body(const int* __restrict__ holes, 
                             const int qpx = s_px[slot];
                             iy = qpx / W; ix = qpx - iy * W;
                             ux = s_dir[0][d]; uy = s_dir[1][d];
-                            inv_umax = 0.999999f / fmaxf(fabsf(ux), fabsf(uy));
-                            // The end is past every valid pixel of its strip once its pixel's coordinate along the direction, t = u . q, is
-                            // more than STRIP_MARGIN beyond the strip's bound.  The pixel k steps on lies within 0.75 of the hole's t -/+ k
-                            // (a unit direction; rounding per axis, < 0.03 of drift), so from k_dead = ceil(|bound - t| + 2.8) steps on that
-                            // holds for sure -- one integer comparison per landing instead of the coordinate's two conversions, a
-                            // multiply-add and a comparison (the ray may die two or three steps later than with the coordinate itself: it
-                            // meets nothing there, that is what the bound says)
+                            inv_umax = jump_inv_umax(ux, uy);
                             k_dead = FILL_MAX_STEPS + 1;
                             if (strips) {
-                                const float2 lh = strips[(size_t) d * bins + ((int) floorf(ux * (float) iy - uy * (float) ix) + s_off[d])];
-                                const float t_hole = ux * (float) ix + uy * (float) iy;
-                                const float room = is_b ? lh.y - t_hole : t_hole - lh.x;            // -inf: nothing on that side at all
-                                k_dead = room > (float) FILL_MAX_STEPS ? FILL_MAX_STEPS + 1 : (int) ceilf(fmaxf(room, -2.0f) + STRIP_MARGIN + 1.8f);
+                                const float2 lh = strips[(size_t) d * bins + (strip_line(strip_across(ux, uy, ix, iy)) + s_off[d])];
+                                const float t_hole = ux * (float) ix + uy * (float) iy;             // strip_along, written out: DESIGN.md section 4
+                                k_dead = strip_k_dead(is_b ? lh.y - t_hole : t_hole - lh.x);        // the room to the strip's bound; -inf: nothing on that side at all
                             }
                             X = axis_enter((float) ix, ux, !is_b);
                             Y = axis_enter((float) iy, uy, !is_b);
@@ -885,7 +662,8 @@ __device__ __forceinline__ void fill_tables_body(const int* __restrict__ holes, 
         // (3)
         const unsigned long long key = s_key[tid];
         if (px >= 0 && key != FILL_NO_ENTRY) {
-            const int d = (int) (key >> 28) & 15, ka = (int) (key >> 14) & FILL_MAX_STEPS, kb = (int) key & FILL_MAX_STEPS;
+            const FillKey win = fill_key_unpack(key);
+            const int d = win.d, ka = win.ka, kb = win.kb;
             const float ddx = s_dir[0][d], ddy = s_dir[1][d];
             const int sax = (int) roundf(advance_exact((float) x, ddx, ka, true, INFINITY)), say = (int) roundf(advance_exact((float) y, ddy, ka, true, INFINITY));
             const int sbx = (int) roundf(advance_exact((float) x, ddx, kb, false, INFINITY)), sby = (int) roundf(advance_exact((float) y, ddy, kb, false, INFINITY));
@@ -898,12 +676,6 @@ __device__ __forceinline__ void fill_tables_body(const int* __restrict__ holes, 
     }
 }
 
-#ifndef KBE_FILL_BLOCK
-#define KBE_FILL_BLOCK 256
-#endif
-#ifndef KBE_FILL_MAX_BLOCKS
-#define KBE_FILL_MAX_BLOCKS 2048
-#endif
 __device__ __forceinline__ void fill_holes_body(const int* __restrict__ holes, const int* __restrict__ hole_count,
                                                     const float* __restrict__ depth, const uint32_t* __restrict__ mask, int W, int H,
                                                     FillDirs dirs, FillRect rect,
@@ -923,7 +695,7 @@ __device__ __forceinline__ void fill_holes_body(const int* __restrict__ holes, c
     }
     if (next_hole_count && blockIdx.x == 0 && threadIdx.x == 0) *next_hole_count = 0;
     const int n = min(*hole_count, W * H);
-    if (tables && n >= tables - 1) return;                      // k_fill_tables, launched in front of this kernel, filled this frame
+    if (!fill_tables_left(tables, n)) return;                   // k_fill_tables, launched in front of this kernel, filled this frame
     // A ray is a straight line, monotone in x and in y.  Once it is outside the bounding box of the valid
     // pixels on a side it is not moving back from, it can never meet one: its outcome is "left the image"
     // (common.py:880-885) without walking there.  Exact, and it is what makes a zoomed-out (dolly) frame,
@@ -1060,11 +832,7 @@ __device__ __forceinline__ void fill_holes_body(const int* __restrict__ holes, c
         const int win = __ffs((int) mine) - 1;                  // lowest lane = lowest direction, its `from` end
         if (lane == win) {
             // lane `win` is the `from` end (even lane); partner values are the `to` end
-            int sxp = ix, syp = iy;
-            if (depth[(size_t) iy * W + ix] < depth[(size_t) oy * W + ox]) { sxp = ox; syp = oy; }     // :904 the farther (background) end
-            const size_t s = (size_t) syp * W + sxp, o = (size_t) px;
-            frame[o * 3] = frame[s * 3]; frame[o * 3 + 1] = frame[s * 3 + 1]; frame[o * 3 + 2] = frame[s * 3 + 2];
-            if (render) for (int c = 0; c < 4; c++) render[c * HW + o] = render[c * HW + s];
+            fill_from(px, ix, iy, ox, oy, depth, W, H, frame, render);
         }
     }
 }
@@ -1103,8 +871,9 @@ __global__ void __launch_bounds__(KBE_FILL_BLOCK) k_fill_holes(FillJobs jobs, in
 }  // namespace
 
 namespace kbe {
-// the hole fill of `n_jobs` frames of the same size (1 or 2): with KBE_STAGE_FILL_DIST the tables and the table-driven fill in
-// front of k_fill_holes (each of them returns at once when a frame has fewer holes than the schedule asks for)
+// the hole fill of `n_jobs` <= KBE_FILL_JOBS frames of the same size: fill the job array, ask the plan (fill_plan), enqueue -- with
+// KBE_STAGE_FILL_DIST the tables and the table-driven fill in front of k_fill_holes (each of them returns at once when a frame has
+// fewer holes than the schedule asks for)
 void launch_fill(hipStream_t s, int n_jobs, const FillTarget* targets, int W, int H, int stages, const FillDirs& dirs, const FillRect& rect, int n_tiles)
 {
     FillJobs jobs;
@@ -1116,23 +885,13 @@ void launch_fill(hipStream_t s, int n_jobs, const FillTarget* targets, int W, in
         j.zkeys = t.sc.zkeys; j.tile_count = t.sc.tile_count; j.bbox = t.sc.bbox; j.coarse = t.sc.coarse; j.dist = t.sc.dist; j.strips = t.sc.strips;
         j.dist_blocks = t.sc.dist_blocks; j.reset_scatter_scratch = t.reset_scatter_scratch; j.next_hole_count = t.next_hole_count;
     }
-    const size_t want_fill = (size_t) W * H / 64, max_fill = (size_t) KBE_FILL_MAX_BLOCKS * 256 / KBE_FILL_BLOCK;       // the same number of threads
-    const unsigned fill_blocks = (unsigned) (want_fill < max_fill ? (want_fill > 0 ? want_fill : 1) : max_fill);
-    int tables = 0;
-    const int fill_mode = (stages & KBE_STAGE_FILL_PER_LANE) ? 1 : ((stages & KBE_STAGE_FILL_PER_HALFWAVE) || !(stages & KBE_STAGE_FILL_BY_COUNT) ? 2 : 0);
-    if ((stages & KBE_STAGE_FILL_DIST) && (stages & (KBE_STAGE_FILL_PER_LANE | KBE_STAGE_FILL_BY_COUNT)) && fill_tables_fit(W, H)) {
-        const int min_holes = (stages & KBE_STAGE_FILL_PER_LANE) ? 0 : KBE_FILL_SERIAL_MIN;
-        const int use_strips = strips_fit(sc0) ? 1 : 0;
-        const int gx = (W + DT_W - 1) / DT_W, gy = (H + DT_H - 1) / DT_H;
-        const int cw = sc0.tiles_x * (TW / 8), ch = sc0.tiles_y * (TH / 8);
-        const int extra = 16 * ((strip_bins(W, H) + 255) / 256) + ((cw + DT_W - 1) / DT_W) * ((ch + DT_H - 1) / DT_H);
-        hipLaunchKernelGGL(k_hole_dist, dim3(gx, gy + (extra + gx - 1) / gx, n_jobs), dim3(256), 0, s, jobs, W, H, min_holes, sc0.tiles_x, sc0.tiles_y, dirs, gy, use_strips);
-        const size_t hw = (size_t) W * H;
-        const unsigned blocks = (unsigned) ((hw + 255) / 256 < KBE_FILL_TABLES_BLOCKS ? (hw + 255) / 256 : KBE_FILL_TABLES_BLOCKS);
-        hipLaunchKernelGGL(k_fill_tables, dim3(blocks, n_jobs), dim3(256), 0, s, jobs, min_holes, W, H, dirs, rect, n_tiles, sc0.tiles_x, sc0.tiles_y, use_strips);
-        tables = 1 + min_holes;                                 // k_fill_holes: a frame is done if it has >= tables - 1 holes
+    const FillPlan P = fill_plan<TW, TH>(W, H, stages, sc0.tiles_x, sc0.tiles_y);
+    if (P.tables) {
+        hipLaunchKernelGGL(k_hole_dist, dim3(P.dist_gx, P.dist_gy, n_jobs), dim3(256), 0, s, jobs, W, H, P.min_holes, sc0.tiles_x, sc0.tiles_y, dirs, P.image_rows, P.use_strips);
+        hipLaunchKernelGGL(k_fill_tables, dim3(P.tables_blocks, n_jobs), dim3(256), 0, s, jobs, P.min_holes, W, H, dirs, rect, n_tiles, sc0.tiles_x, sc0.tiles_y, P.use_strips);
     }
-    hipLaunchKernelGGL(k_fill_holes, dim3(fill_blocks, n_jobs), dim3(KBE_FILL_BLOCK), 0, s, jobs, W, H, dirs, rect, n_tiles, fill_mode, sc0.tiles_x, sc0.tiles_y, tables);
+    hipLaunchKernelGGL(k_fill_holes, dim3(P.fill_blocks, n_jobs), dim3(KBE_FILL_BLOCK), 0, s, jobs, W, H, dirs, rect, n_tiles, P.fill_mode, sc0.tiles_x, sc0.tiles_y,
+                       fill_tables_arg(P.tables, P.min_holes));
 }
 
 }  // namespace kbe

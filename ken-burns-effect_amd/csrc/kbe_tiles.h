@@ -34,9 +34,6 @@ namespace kbe {
 #define KBE_BUCKET_FACTOR 12
 #endif
 constexpr int TW = KBE_TILE_W, TH = KBE_TILE_H;     // target tile owned by one workgroup
-// strip tables of the hole fill (k_hole_dist): per fill direction, W + H + 8 lines of (lo, hi); built from the extents of
-// up to STRIP_TILES tile rows / columns
-constexpr int STRIP_TILES = 512;
 constexpr int KW = TW + 2, KH = TH + 2;             // tile + the 1-px halo whose z the degrid reads
 constexpr int BW = TW + 1, BH = TH + 1;             // bins: north-west corners x0-1 .. x0+TW-1, y0-1 .. y0+TH-1
 constexpr int TILE_THREADS = KBE_TILE_THREADS;
@@ -129,7 +126,7 @@ struct FillRect { int x0, y0, x1, y1; };    // inclusive; only holes inside are 
 #define KBE_FILL_BY_COUNT_MIN_LANES 2       // frames in flight from which the video loop lets the fill pick its schedule by the hole count
 #endif
 
-// kbe_holes.hip: the hole fill of one frame, or of two frames of the same size in the same launches -- with
+// kbe_holes.hip: the hole fill of up to KBE_FILL_JOBS frames of the same size in the same launches -- with
 // KBE_STAGE_FILL_DIST the tables (k_hole_dist) and the table-driven fill (k_fill_tables) in front of k_fill_holes; each
 // returns at once when a frame has fewer holes than its schedule asks for
 constexpr int KBE_FILL_JOBS = 4;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: throughput (default lanes and 1 lane) for the three workloads, per variant build (dev aid)
-#   gpurun -- 'bash tools/gpu_cases.sh "" "-DKBE_PROBE_FILL_GLOBAL"'
+#   bash tools/gpu_cases.sh "" "-DKBE_FILL_BURST=8"
 export HSA_ENABLE_IPC_MODE_LEGACY=0 MIOPEN_FIND_MODE=FAST
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
