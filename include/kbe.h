@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define KBE_ABI_VERSION 11
+#define KBE_ABI_VERSION 12
 
 /* the library is built with -fvisibility=hidden; only these entry points are exported */
 #if defined(__GNUC__)
@@ -496,6 +496,29 @@ KBE_API int kbe_bias_act(const float* x, const float* bias, const float* slope, 
    Source positions and weights as PyTorch's upsample_bilinear2d computes them (0.5 (dst + 0.5) - 0.5 clamped at 0, the
    neighbour clamped at the edge). */
 KBE_API int kbe_upsample2x_act(const float* x, const float* slope, int B, int C, int H, int W, float* out, kbe_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Motion-JPEG on the device: frames that lie in HBM (kbe_render_video with host_out = device memory, common.render_frames with
+ * keep_on_device) leave as baseline JPEG streams -- about a tenth of the bytes -- for the video writers (pipeline.write_mjpeg_mp4 / _avi).
+ *
+ * The picture is the one libkbe_jpeg.so writes (baseline sequential DCT, 8 bits, JFIF YCbCr 4:2:0, the Annex K.1 tables under the IJG
+ * quality rule, the Annex K.3 Huffman tables, edge pixels repeated into partial MCUs) with RESTART INTERVALS: a DRI segment, every
+ * interval byte-aligned with its DC predictors at 0 and followed by RSTm -- the independent units of work of the kernels.  The stream is
+ * defined byte for byte by csrc/kbe_mjpeg_block.h executed serially on a CPU (tests/mjpeg_check.cpp).
+ *
+ * kbe_mjpeg_encode: frames_u8 = HOST array of n_frames DEVICE pointers to [H][stride_bytes] rows of 3-byte pixels (R, G, B; B, G, R with
+ * KBE_MJPEG_BGR); quality 1..100; W, H <= 65535; any n_frames >= 1 (the entry cuts them into launches).  Frame i's stream is
+ * streams[offsets[i] .. offsets[i + 1]), the streams back to back; offsets: DEVICE [n_frames + 1], 8-byte aligned.  If the streams need more
+ * than `cap` bytes, *status (DEVICE) is 1, the offsets still hold the true sizes and no byte at or beyond cap is written; else 0.
+ * kbe_mjpeg_bound: bytes that hold ANY W x H frame's stream (the true worst case).  scratch: kbe_mjpeg_scratch_bytes(W, H, n_frames)
+ * bytes, 8-byte aligned, contents irrelevant: 12 bytes per restart interval of at most 12 frames -- it does not grow with the streams.
+ * Every argument is validated before anything is enqueued; nothing is allocated; all launches are asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------- */
+#define KBE_MJPEG_BGR 1
+KBE_API size_t kbe_mjpeg_bound(int W, int H);
+KBE_API size_t kbe_mjpeg_scratch_bytes(int W, int H, int n_frames);
+KBE_API int kbe_mjpeg_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H, int stride_bytes, int quality, int flags,
+                             void* scratch, uint8_t* streams, size_t cap, uint64_t* offsets, int* status, kbe_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -354,15 +354,18 @@ def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_o
     return out if keep_on_device else out.cpu().numpy()
 
 
-def process_kenburns(objectSettings, objectCommon, moduleInpaint):
+def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False):
     """Renders the camera path ``dblSteps`` between two crop windows (common.py:172-263).
 
     objectSettings: dblSteps, objectFrom/objectTo {dblCenterU, dblCenterV, intCropWidth,
     intCropHeight}, boolInpaint (default True), dolly.  Returns a list of uint8 HxWx3 frames.
-    Optional key ``boolCrop`` (default True): apply the crop + resize of :256-257."""
+    Optional key ``boolCrop`` (default True): apply the crop + resize of :256-257.  ``keep_on_device``: the frames stay in HBM and
+    come back as one uint8 [n,H,W,3] device tensor (for the device-side Motion-JPEG encoder)."""
     with on_device_of(objectCommon['tensorRawPoints']):
         if 'boolInpaint' not in objectSettings or objectSettings['boolInpaint'] == True:   # noqa: E712
             build_pointcloud(objectSettings, objectCommon, moduleInpaint)
         crop = crop_size(objectSettings) if objectSettings.get('boolCrop', True) else None
-        frames = render_frames(frame_cameras(objectSettings, objectCommon), objectCommon, crop)
+        frames = render_frames(frame_cameras(objectSettings, objectCommon), objectCommon, crop, keep_on_device=keep_on_device)
+    if keep_on_device:
+        return frames
     return [frames[i] for i in range(frames.shape[0])]

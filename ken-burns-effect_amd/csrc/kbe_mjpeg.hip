@@ -1,0 +1,283 @@
+// kbe_mjpeg.hip -- kbe_mjpeg_encode: frames that lie in HBM as baseline JPEG streams, back to back, for the Motion-JPEG video writers
+// (include/kbe.h).  The stream and all of its arithmetic are defined in kbe_mjpeg_block.h; this file spreads that work over the chip.
+//
+// A frame's restart intervals (kRestartMcus MCUs each) are independent, but where an interval's bytes go depends on the lengths of all
+// intervals in front of it.  So the work is done twice, with nothing but 12 bytes per interval in HBM between the two passes:
+//   1. k_mjpeg_encode<false>: a workgroup takes kGroupIntervals intervals: samples (colour conversion, chroma average), the 8 x 8 DCTs with
+//      eight lanes per block (rows in registers, transpose through LDS, columns), quantisation into LDS; then one lane per BLOCK packs the
+//      block's Huffman codes and value bits into words of its own in LDS, and one lane per interval sends them on, in order, into a sink
+//      that counts the stream's bytes (stuffed 0xFF, padding, RSTm): the interval's LENGTH is all that is stored;
+//   2. an exclusive scan of the lengths over all intervals of all frames of the launch (sums of 256, a scan of the sums, apply): every
+//      interval's place, every frame's offsets[i], the total and `status`;
+//   3. k_mjpeg_encode<true>: the same code again, the sink now storing the bytes at their place (nothing at or beyond `cap`).
+// No kernel waits for another workgroup.  n frames are cut into launches of kFramesPerLaunch.
+#include "kbe_host.h"
+#include "kbe_mjpeg_block.h"
+
+using namespace kbe;
+using namespace kbe_mjpeg;
+
+namespace {
+
+constexpr int kFramesPerLaunch = 12;
+constexpr int kGroupIntervals = 4;                                              // intervals per workgroup: one per wave in the entropy phase
+constexpr int kGroupBlocks = kGroupIntervals * kRestartMcus * 6;                // 96 blocks
+constexpr int kEncodeThreads = 64 * kGroupIntervals;
+constexpr int kBlocksAtOnce = kEncodeThreads / 8;                               // eight lanes per block
+constexpr int kScanThreads = 256;                                               // intervals per workgroup of the scan
+constexpr int kSumsThreads = 64;                                                // sums the scan of the sums takes at once
+static_assert(kGroupBlocks % kBlocksAtOnce == 0, "the DCT loop takes whole rounds");
+
+struct EncodeArgs {
+    const uint8_t* frames[kFramesPerLaunch];
+    Geometry g;
+    Tables t;
+};
+static_assert(sizeof(EncodeArgs) <= 3840, "kernel arguments: 4 KB at most");
+
+struct CountSink {
+    uint32_t n;
+    __device__ __forceinline__ void put(unsigned) { n++; }
+};
+
+// bytes to their place: singly up to the first 4-byte boundary, then four at a time, the rest singly; never at or beyond cap
+struct StoreSink {
+    uint8_t* base;
+    uint64_t pos, cap;
+    uint32_t word;
+    int k;
+    __device__ __forceinline__ void put(unsigned v)
+    {
+        if (k == 0 && (((uintptr_t) base + pos) & 3u)) {
+            if (pos < cap) base[pos] = (uint8_t) v;
+            pos++;
+            return;
+        }
+        word |= v << (8 * k);
+        if (++k == 4) {
+            if (pos + 4 <= cap) *reinterpret_cast<uint32_t*>(base + pos) = word;
+            else tail();
+            pos += 4;
+            word = 0;
+            k = 0;
+        }
+    }
+    __device__ __forceinline__ void tail()
+    {
+        for (int i = 0; i < k; i++)
+            if (pos + i < cap) base[pos + i] = (uint8_t) (word >> (8 * i));
+    }
+    __device__ __forceinline__ void finish() { tail(); pos += k; k = 0; }
+};
+
+template <bool STORE>
+__global__ __launch_bounds__(kEncodeThreads) void k_mjpeg_encode(const EncodeArgs a, uint32_t* __restrict__ counts, const uint64_t* __restrict__ starts,
+                                                                 uint8_t* __restrict__ streams, uint64_t cap)
+{
+    __shared__ int16_t s_zz[kGroupBlocks * 64];
+    // (the DCT's transposes, then the blocks' packed bits: one after the other in the same bytes)
+    __shared__ __attribute__((aligned(16))) uint32_t s_raw[kGroupBlocks * kBlockWords];
+    __shared__ int s_nbits[kGroupBlocks];
+    static_assert(sizeof(s_raw) >= sizeof(float) * kBlocksAtOnce * 8 * 9, "the transposes fit");
+    float (*s_tr)[8][9] = reinterpret_cast<float (*)[8][9]>(s_raw);
+    __shared__ float s_rq[2][64];
+    __shared__ uint32_t s_dc[2][12], s_ac[2][256];
+    __shared__ uint8_t s_scan[64];
+
+    const int tid = (int) threadIdx.x, frame = (int) blockIdx.y;
+    const Geometry g = a.g;
+    const int interval0 = (int) blockIdx.x * kGroupIntervals;
+    for (int i = tid; i < 128; i += kEncodeThreads) (&s_rq[0][0])[i] = (&a.t.rq[0][0])[i];
+    for (int i = tid; i < 512; i += kEncodeThreads) (&s_ac[0][0])[i] = (&a.t.ac[0][0])[i];
+    if (tid < 24) (&s_dc[0][0])[tid] = (&a.t.dc[0][0])[tid];
+    if (tid < 64) s_scan[tid] = a.t.scan_of[tid];
+    __syncthreads();
+
+    // samples, DCT, quantisation: eight lanes per block, lane r takes row r and then column r
+    const uint8_t* src = a.frames[frame];
+    const int lane = tid & 7, slot = tid >> 3;
+    for (int round = 0; round < kGroupBlocks / kBlocksAtOnce; round++) {
+        const int blk = round * kBlocksAtOnce + slot, comp = blk % 6;
+        const int mcu = interval0 * kRestartMcus + blk / 6;
+        const bool live = mcu < g.mcus;
+        float v[8];
+        if (live) {
+            block_row(src, g, mcu % g.mcus_x, mcu / g.mcus_x, comp, lane, v);
+            fdct8(v);
+            for (int j = 0; j < 8; j++) s_tr[slot][lane][j] = v[j];
+        }
+        __syncthreads();
+        if (live) {
+            for (int i = 0; i < 8; i++) v[i] = s_tr[slot][i][lane];
+            block_column(v, lane, s_rq[comp < 4 ? 0 : 1], s_scan, s_zz + blk * 64);
+        }
+        __syncthreads();
+    }
+
+    // entropy coding, step 1: one lane per block packs the block's bits into words of its own (a block's bits depend on its coefficients
+    // and the DC value in front of it, nothing else)
+    if (tid < kGroupBlocks) {
+        const int k = tid / (kRestartMcus * 6), within = tid % (kRestartMcus * 6), comp = within % 6;
+        const int interval = interval0 + k;
+        if (interval < g.intervals && within < interval_mcus(g, interval) * 6) {
+            PackedBits packed = { s_raw + tid * kBlockWords, 0, 0, 0 };
+            const int16_t* zz = s_zz + k * kRestartMcus * 6 * 64;
+            encode_block(packed, zz + within * 64, s_dc[comp < 4 ? 0 : 1], s_ac[comp < 4 ? 0 : 1], dc_predictor(zz, within / 6, comp), nullptr);
+            s_nbits[tid] = packed.finish();
+        }
+    }
+    __syncthreads();
+
+    // step 2: an interval's bytes are a serial chain (stuffing, the stream's byte boundaries): lane 0 of wave k sends the bits of interval
+    // k's blocks on, in order, into a sink that counts or stores
+    const size_t first = (size_t) frame * (size_t) g.intervals;
+    if ((tid & 63) == 0) {
+        const int k = tid >> 6, interval = interval0 + k;
+        if (interval < g.intervals) {
+            const int blocks = interval_mcus(g, interval) * 6, blk0 = k * kRestartMcus * 6;
+            const uint32_t lead = interval == 0 ? (uint32_t) kHeaderBytes : 0u;        // a frame's header lies in front of its first interval
+            if (!STORE) {
+                CountSink sink = { 0u };
+                StreamBits<CountSink> out = { { 0u, 0 }, sink, nullptr };
+                for (int blk = 0; blk < blocks; blk++) replay_bits(out, s_raw + (blk0 + blk) * kBlockWords, s_nbits[blk0 + blk]);
+                end_interval(out.b, sink, g, interval, nullptr);
+                counts[first + interval] = sink.n + lead;
+            } else {
+                StoreSink sink = { streams, starts[first + interval] + lead, cap, 0u, 0 };
+                StreamBits<StoreSink> out = { { 0u, 0 }, sink, nullptr };
+                for (int blk = 0; blk < blocks; blk++) replay_bits(out, s_raw + (blk0 + blk) * kBlockWords, s_nbits[blk0 + blk]);
+                end_interval(out.b, sink, g, interval, nullptr);
+                sink.finish();
+            }
+        }
+    }
+    if (STORE && interval0 == 0) {
+        const uint64_t at = starts[first];
+        for (int b = tid; b < kHeaderBytes; b += kEncodeThreads)
+            if (at + b < cap) streams[at + b] = a.t.header[b];
+    }
+}
+
+// exclusive scan of one value per thread over a workgroup of THREADS; *total: the sum
+template <int THREADS>
+__device__ __forceinline__ uint64_t group_exclusive_scan(uint64_t v, uint64_t* lds, uint64_t* total)
+{
+    const int t = (int) threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (int d = 1; d < THREADS; d <<= 1) {
+        const uint64_t below = t >= d ? lds[t - d] : 0;
+        __syncthreads();
+        lds[t] += below;
+        __syncthreads();
+    }
+    const uint64_t inclusive = lds[t];
+    *total = lds[THREADS - 1];
+    __syncthreads();
+    return inclusive - v;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_mjpeg_sums(const uint32_t* __restrict__ counts, size_t n, uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t lds[kScanThreads];
+    const size_t at = (size_t) blockIdx.x * kScanThreads + threadIdx.x;
+    uint64_t total;
+    group_exclusive_scan<kScanThreads>(at < n ? counts[at] : 0u, lds, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// one workgroup: the sums become where their kScanThreads intervals start; offsets[f0] carries on from the launch before; the total and `status`
+__global__ __launch_bounds__(kSumsThreads) void k_mjpeg_scan_sums(uint64_t* __restrict__ sums, size_t n_sums, uint64_t* __restrict__ offsets, int f0, int nf, uint64_t cap,
+                                                                  int* __restrict__ status)
+{
+    __shared__ uint64_t lds[kSumsThreads];
+    uint64_t carry = f0 == 0 ? 0 : offsets[f0];
+    for (size_t at = 0; at < n_sums; at += kSumsThreads) {
+        const size_t i = at + threadIdx.x;
+        const uint64_t mine = i < n_sums ? sums[i] : 0;
+        uint64_t total;
+        const uint64_t before = group_exclusive_scan<kSumsThreads>(mine, lds, &total);
+        if (i < n_sums) sums[i] = carry + before;
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        offsets[f0 + nf] = carry;
+        *status = carry > cap ? 1 : 0;              // (the totals grow from launch to launch: the last launch's word is the call's)
+    }
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_mjpeg_starts(const uint32_t* __restrict__ counts, size_t n, const uint64_t* __restrict__ sums, int intervals,
+                                                               uint64_t* __restrict__ starts, uint64_t* __restrict__ offsets, int f0)
+{
+    __shared__ uint64_t lds[kScanThreads];
+    const size_t at = (size_t) blockIdx.x * kScanThreads + threadIdx.x;
+    uint64_t total;
+    const uint64_t start = sums[blockIdx.x] + group_exclusive_scan<kScanThreads>(at < n ? counts[at] : 0u, lds, &total);
+    if (at < n) {
+        starts[at] = start;
+        if (at % (size_t) intervals == 0) offsets[f0 + at / (size_t) intervals] = start;       // a frame's first interval: where its stream starts
+    }
+}
+
+struct ScratchLayout { size_t counts, starts, sums, bytes; };       // byte offsets
+
+ScratchLayout scratch_layout(int W, int H, int n_frames)
+{
+    const Geometry g = geometry(W, H, 0, 0);
+    const size_t n = (size_t) (n_frames < kFramesPerLaunch ? n_frames : kFramesPerLaunch) * (size_t) g.intervals;
+    ScratchLayout s;
+    s.counts = 0;
+    s.starts = (n * 4 + 7) & ~(size_t) 7;
+    s.sums = s.starts + n * 8;
+    s.bytes = s.sums + ((n + kScanThreads - 1) / kScanThreads) * 8;
+    return s;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t kbe_mjpeg_bound(int W, int H)
+{
+    return W > 0 && H > 0 && W <= 65535 && H <= 65535 ? stream_bound(W, H) : 0;
+}
+
+size_t kbe_mjpeg_scratch_bytes(int W, int H, int n_frames)
+{
+    return W > 0 && H > 0 && W <= 65535 && H <= 65535 && n_frames > 0 ? scratch_layout(W, H, n_frames).bytes : 0;
+}
+
+int kbe_mjpeg_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H, int stride_bytes, int quality, int flags, void* scratch, uint8_t* streams, size_t cap,
+                     uint64_t* offsets, int* status, kbe_stream_t stream)
+{
+    KBE_REQUIRE(frames_u8 && n_frames >= 1 && W > 0 && H > 0 && W <= 65535 && H <= 65535, "kbe_mjpeg_encode: bad frames or size");
+    KBE_REQUIRE(stride_bytes >= 3 * W && quality >= 1 && quality <= 100 && (flags & ~KBE_MJPEG_BGR) == 0, "kbe_mjpeg_encode: bad stride, quality or flags");
+    KBE_REQUIRE(scratch && ((uintptr_t) scratch & 7) == 0 && offsets && ((uintptr_t) offsets & 7) == 0 && status && (streams || cap == 0), "kbe_mjpeg_encode: bad buffers");
+    for (int i = 0; i < n_frames; i++) KBE_REQUIRE(frames_u8[i], "kbe_mjpeg_encode: null frame");
+
+    EncodeArgs a;
+    a.g = geometry(W, H, stride_bytes, flags);
+    host::tables_build(W, H, quality, &a.t);
+    const ScratchLayout lay = scratch_layout(W, H, n_frames);
+    uint32_t* counts = (uint32_t*) ((char*) scratch + lay.counts);
+    uint64_t* starts = (uint64_t*) ((char*) scratch + lay.starts);
+    uint64_t* sums = (uint64_t*) ((char*) scratch + lay.sums);
+    hipStream_t s = (hipStream_t) stream;
+    const unsigned groups = (unsigned) ((a.g.intervals + kGroupIntervals - 1) / kGroupIntervals);
+
+    for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
+        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
+        for (int i = 0; i < kFramesPerLaunch; i++) a.frames[i] = i < nf ? frames_u8[f0 + i] : nullptr;
+        const size_t n = (size_t) nf * (size_t) a.g.intervals, n_sums = (n + kScanThreads - 1) / kScanThreads;
+        hipLaunchKernelGGL(k_mjpeg_encode<false>, dim3(groups, (unsigned) nf), dim3(kEncodeThreads), 0, s, a, counts, (const uint64_t*) starts, streams, (uint64_t) cap);
+        hipLaunchKernelGGL(k_mjpeg_sums, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, sums);
+        hipLaunchKernelGGL(k_mjpeg_scan_sums, dim3(1), dim3(kSumsThreads), 0, s, sums, n_sums, offsets, f0, nf, (uint64_t) cap, status);
+        hipLaunchKernelGGL(k_mjpeg_starts, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, (const uint64_t*) sums, a.g.intervals, starts, offsets, f0);
+        hipLaunchKernelGGL(k_mjpeg_encode<true>, dim3(groups, (unsigned) nf), dim3(kEncodeThreads), 0, s, a, counts, (const uint64_t*) starts, streams, (uint64_t) cap);
+        const int rc = launched("kbe_mjpeg_encode");
+        if (rc != KBE_OK) return rc;
+    }
+    return KBE_OK;
+}
+
+}  // extern "C"

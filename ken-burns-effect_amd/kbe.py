@@ -5,6 +5,7 @@
         [--pretrained-estim] [--2d] [--startU/--startV/--endU/--endV/--startW/--startH/--endW/--endH N]
         [--semantics-path vgg19_bn_state_dict.pth]     (new: the reference downloads these weights through torchvision)
         [--allow-random-weights]                       (new: render with seeded weights where a checkpoint is missing instead of failing)
+        [--jpeg native|pillow|device]                  (new: who encodes a Motion-JPEG video's frames -- host threads, Pillow, or the GPU: env KBE_JPEG)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -17,12 +18,12 @@ import numpy as np
 import torch
 
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
-                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights']
+                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=']
 
 
 def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
-           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False,
+           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -80,6 +81,11 @@ def main(argv=None):
     from .pipeline import Pipeline
     torch.set_grad_enabled(False)
     cfg, window = parse(sys.argv[1:] if argv is None else argv)
+    if cfg['jpeg'] is not None:
+        if cfg['jpeg'] not in ('native', 'pillow', 'device'):
+            raise SystemExit('--jpeg %s: native, pillow or device' % cfg['jpeg'])
+        import os
+        os.environ['KBE_JPEG'] = cfg['jpeg']        # (the writers read the switch where they encode: pipeline.jpeg_encoder)
     image = load_image(cfg['in'], cfg['pretrained-estim'])
     zoom = windows_for(image.shape[3], image.shape[2], window, cfg['dolly'])
     paths = [cfg['estim-path'], cfg['refine-path'], cfg['inpaint-path']] + ([cfg['inpaint-depth']] if cfg['inpaint-depth'] else [])

@@ -134,9 +134,20 @@ class Pipeline():
             self.estimate(tensorImage)
             if inpaint_depth:
                 raise NotImplementedError('two-network depth inpainting is broken in the reference (common.py:50-69)')
+            # KBE_JPEG=device, a Motion-JPEG video (no ffmpeg binary) and no PNG frames: the frames stay in HBM, the GPU encodes them and the
+            # streams come to the host, a tenth of the pixels' bytes; any other combination takes the host route below
+            on_device = output_path is not None and not self.output_frames and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
             frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                               'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
-                                              'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint)
+                                              'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device)
+        if on_device:
+            os.makedirs(output_path, exist_ok=True)
+            # (the frames are in the INPUT's channel order, as below: the encoder reads B, G, R unless --pretrained-estim)
+            encoded = jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=not pretrained_estim)
+            # forth and back (:131): every distinct frame was encoded once, the way back is the same byte objects again
+            write_video(os.path.join(output_path, '3d_kbe.mp4'), None, fps=25, jpegs=encoded + encoded[-2::-1], frame_size=tuple(frames.shape[1:3]))
+            host = frames.cpu().numpy()                                                 # the return value, fetched after the video is written
+            return [host[i] for i in range(host.shape[0])]
         if output_path is not None:
             os.makedirs(output_path, exist_ok=True)
             # channel order on disk as the reference produces it: frames are in the INPUT's channel order
@@ -163,10 +174,15 @@ def _writer_pool_size(n_jobs):
 def jpeg_encoder():
     """'native' (libkbe_jpeg.so, include/kbe_jpeg.h: a batch of frames on host threads) or 'pillow' (one frame at a time: Pillow's encoder
     holds the interpreter lock -- measured, 8 threads: 201 ms against 171 ms on one).  KBE_JPEG=pillow forces the latter; a missing
-    library falls back to it with a warning (the writers are host-side conveniences, not the render path: that one has no fallback)."""
+    library falls back to it with a warning (the writers are host-side conveniences, not the render path: that one has no fallback).
+    KBE_JPEG=device: the GPU encodes (kbe_mjpeg_encode, include/kbe.h; the second item is then the kernel set, whose mjpeg_encode takes
+    frames in HBM) -- opt-in; the same picture with restart intervals in its stream.  No fallback: without the HIP library it raises."""
     global _jpeg_lib
     if os.environ.get('KBE_JPEG', 'native') == 'pillow':
         return 'pillow', None
+    if os.environ.get('KBE_JPEG', 'native') == 'device':
+        from . import _native
+        return 'device', _native.kernels()
     if _jpeg_lib is None:
         import ctypes
         if not os.path.exists(_JPEG_LIB_PATH):
@@ -221,12 +237,22 @@ def write_frames(frames_dir, frames_rgb):
     _on_threads(list(enumerate(frames_rgb)), save)
 
 
-def write_mjpeg_avi(path, frames_rgb, fps=25, quality=92):
+def _encoded(frames_rgb, quality, jpegs, frame_size):
+    """(the streams, (h, w)) of a writer's call: pre-encoded ``jpegs`` (one bytes object per frame, with ``frame_size`` = (h, w)), or the
+    frames encoded here."""
+    if jpegs is not None:
+        if frame_size is None or not len(jpegs):
+            raise ValueError('pre-encoded jpegs= need frame_size=(h, w) and at least one frame')
+        return list(jpegs), (int(frame_size[0]), int(frame_size[1]))
+    return _jpegs(frames_rgb, quality), tuple(frames_rgb[0].shape[:2])
+
+
+def write_mjpeg_avi(path, frames_rgb, fps=25, quality=92, jpegs=None, frame_size=None):
     """A playable video without any external encoder: Motion-JPEG in an AVI container (RIFF 'AVI ' with one 'vids' / 'MJPG' stream,
-    an 'idx1' index; every frame a baseline JPEG from PIL).  What write_video writes for an ``.avi`` where there is no ffmpeg binary."""
+    an 'idx1' index; every frame a baseline JPEG from PIL).  What write_video writes for an ``.avi`` where there is no ffmpeg binary.
+    ``jpegs`` / ``frame_size``: frames that are encoded already (_encoded); frames_rgb is then not looked at."""
     import struct
-    h, w = frames_rgb[0].shape[:2]
-    jpegs = _jpegs(frames_rgb, quality)
+    jpegs, (h, w) = _encoded(frames_rgb, quality, jpegs, frame_size)
     n = len(jpegs)
     biggest = max(len(j) for j in jpegs)
 
@@ -286,6 +312,11 @@ def _jpegs(frames_rgb, quality):
             if rc != 0:
                 raise RuntimeError('kbe_jpeg_encode_batch: %d' % rc)
             encoded += [outs[i][:got[i]].tobytes() for i in range(n)]
+    elif kind == 'device' and len(sizes) == 1:
+        import torch
+        # (frames that are on the host already: uploaded as one batch; Pipeline hands the encoder its frames where they lie, in HBM)
+        stacked = torch.from_numpy(np.stack([np.ascontiguousarray(f, dtype=np.uint8) for f in distinct]))
+        encoded = lib.mjpeg_encode(stacked.cuda(), int(quality))
     else:
         import io
         from PIL import Image
@@ -298,14 +329,14 @@ def _jpegs(frames_rgb, quality):
     return [encoded[first[id(frame)]] for frame in frames_rgb]
 
 
-def write_mjpeg_mp4(path, frames_rgb, fps=25, quality=92):
+def write_mjpeg_mp4(path, frames_rgb, fps=25, quality=92, jpegs=None, frame_size=None):
     """An ``.mp4`` without any external encoder: an ISO base media file (ISO/IEC 14496-12) with one video track whose samples are
     baseline JPEGs (PIL) -- sample entry ``mp4v`` with an ``esds`` whose objectTypeIndication is 0x6C, "Visual ISO/IEC 10918-1
     (JPEG)", the registered way of carrying Motion-JPEG in MP4 (what ffmpeg's mp4 muxer writes for ``-c:v mjpeg``; ffmpeg-based
-    players, VLC and mpv decode it).  Layout: ftyp, mdat (the samples, one chunk), moov (every sample a sync sample: no stss)."""
+    players, VLC and mpv decode it).  Layout: ftyp, mdat (the samples, one chunk), moov (every sample a sync sample: no stss).
+    ``jpegs`` / ``frame_size``: frames that are encoded already (_encoded); frames_rgb is then not looked at."""
     import struct
-    jpegs = _jpegs(frames_rgb, quality)
-    h, w = frames_rgb[0].shape[:2]
+    jpegs, (h, w) = _encoded(frames_rgb, quality, jpegs, frame_size)
     n, delta = len(jpegs), 512
     timescale = int(fps) * delta
     duration = n * delta
@@ -352,17 +383,20 @@ def write_mjpeg_mp4(path, frames_rgb, fps=25, quality=92):
     return path
 
 
-def write_video(path, frames_rgb, fps=25):
+def write_video(path, frames_rgb, fps=25, jpegs=None, frame_size=None):
     """mpeg4 through an ffmpeg pipe when the binary exists (what moviepy does, pipeline.py:132-134).  Without one the video is still
     written, under the name asked for, with the encoder this package carries: Motion-JPEG -- in an MP4 container for an ``.mp4``
-    (write_mjpeg_mp4), in an AVI for an ``.avi`` (write_mjpeg_avi) -- and the function says so and returns False."""
+    (write_mjpeg_mp4), in an AVI for an ``.avi`` (write_mjpeg_avi) -- and the function says so and returns False.  ``jpegs`` /
+    ``frame_size``: the frames as Motion-JPEG streams encoded already (the writers' arguments); only the Motion-JPEG route can take them."""
     ffmpeg = shutil.which('ffmpeg')
-    h, w = frames_rgb[0].shape[:2]
     if ffmpeg is None:
         writer = write_mjpeg_avi if path.lower().endswith('.avi') else write_mjpeg_mp4
-        writer(path, frames_rgb, fps)
-        print('ffmpeg not found: %s holds Motion-JPEG (%d frames at %d fps) instead of mpeg4' % (path, len(frames_rgb), fps))
+        writer(path, frames_rgb, fps, jpegs=jpegs, frame_size=frame_size)
+        print('ffmpeg not found: %s holds Motion-JPEG (%d frames at %d fps) instead of mpeg4' % (path, len(jpegs if jpegs is not None else frames_rgb), fps))
         return False
+    if frames_rgb is None:
+        raise ValueError('write_video: pre-encoded jpegs= are Motion-JPEG; the ffmpeg route needs the frames')
+    h, w = frames_rgb[0].shape[:2]
     proc = subprocess.Popen([ffmpeg, '-y', '-loglevel', 'error', '-f', 'rawvideo', '-pix_fmt', 'rgb24', '-s', '%dx%d' % (w, h),
                              '-r', str(fps), '-i', '-', '-c:v', 'mpeg4', path], stdin=subprocess.PIPE)
     for frame in frames_rgb:
