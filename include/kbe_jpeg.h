@@ -1,5 +1,6 @@
 /*
- * kbe_jpeg.h -- C ABI of libkbe_jpeg.so: the frame writers' baseline-JPEG encoder (HOST code; ken-burns-effect_amd/csrc/kbe_jpeg.c).
+ * kbe_jpeg.h -- C ABI of libkbe_jpeg.so: the frame writers' baseline-JPEG encoder (HOST code; ken-burns-effect_amd/csrc/kbe_jpeg.cpp,
+ * whose picture and stream are defined in csrc/kbe_mjpeg_block.h, the definition it shares with the device encoder kbe_mjpeg_encode).
  *
  * What it replaces.  The reference hands its finished uint8 frames to moviepy, which pipes them into an ffmpeg process
  * (`ImageSequenceClip(...).write_videofile(..., codec='mpeg4')`, /root/reference/utils/pipeline.py:130-134).  Where there is
@@ -30,7 +31,10 @@ extern "C" {
 
 enum { KBE_JPEG_OK = 0, KBE_JPEG_E_INVALID = -1, KBE_JPEG_E_SPACE = -2 /* `cap` too small: ask kbe_jpeg_bound */ };
 
-/* bytes that hold any w x h frame's JPEG */
+/* a PRACTICAL bound on a w x h frame's JPEG: 1024 bytes of headers + 4 bytes per coefficient.  A coefficient takes at most 16 code + 10
+ * value bits, so the bound holds every stream of which no more than about a fifth of the bytes are 0xFF (each takes a stuffed zero byte
+ * after it) -- every picture, and noise at quality 100; it is not the format's worst case, in which every byte is stuffed.  A stream that
+ * does not fit is refused with KBE_JPEG_E_SPACE, never written past `cap`. */
 KBE_JPEG_API size_t kbe_jpeg_bound(int w, int h);
 /* one frame -> out[0 .. *size) */
 KBE_JPEG_API int kbe_jpeg_encode(const uint8_t* rgb, int w, int h, int stride_bytes, int quality, uint8_t* out, size_t cap, size_t* size);

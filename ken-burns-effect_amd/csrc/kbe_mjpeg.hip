@@ -257,7 +257,7 @@ int kbe_mjpeg_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H
 
     EncodeArgs a;
     a.g = geometry(W, H, stride_bytes, flags);
-    host::tables_build(W, H, quality, &a.t);
+    host::tables_build(W, H, quality, &a.t, kRestartMcus);
     const ScratchLayout lay = scratch_layout(W, H, n_frames);
     uint32_t* counts = (uint32_t*) ((char*) scratch + lay.counts);
     uint64_t* starts = (uint64_t*) ((char*) scratch + lay.starts);

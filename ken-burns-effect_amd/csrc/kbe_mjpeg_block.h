@@ -1,11 +1,14 @@
-// kbe_mjpeg_block.h -- the device-side Motion-JPEG encoder's arithmetic and stream format (kbe_mjpeg.hip), each piece defined ONCE and
-// compiled twice: by hipcc into the kernels, and by g++ into tests/mjpeg_check.cpp, whose encode_frame below runs the same pieces one
-// after the other on the host.  The device's stream is, byte for byte, what encode_frame writes (tests/test_mjpeg_gpu.py).
+// kbe_mjpeg_block.h -- the project's ONE definition of its baseline JPEG: the arithmetic and the stream format of both Motion-JPEG encoders.
+// Three compilations read it: hipcc into the kernels of kbe_mjpeg.hip (the device encoder), g++ into tests/mjpeg_check.cpp (the device
+// encoder's CPU twin, whose encode_frame below runs the same pieces one after the other), and g++ into kbe_jpeg.cpp (libkbe_jpeg.so, the
+// host encoder on threads).  The device's stream is, byte for byte, what encode_frame writes (tests/test_mjpeg_gpu.py).
 //
-// The picture is the one kbe_jpeg.c writes (baseline sequential DCT, 8 bits, JFIF YCbCr 4:2:0, the Annex K.1 tables under the IJG quality
-// rule, the Annex K.3 Huffman tables, edge pixels repeated into partial MCUs) plus RESTART INTERVALS: a DRI segment declares intervals of
-// kRestartMcus MCUs; every interval starts on a byte boundary with the DC predictors at 0, ends padded with 1-bits and is followed by
-// RSTm, m = 0..7 in turn (none after the last).  Intervals are then independent: the unit of work of the kernels.
+// The picture: baseline sequential DCT (ISO/IEC 10918-1), 8 bits, JFIF YCbCr 4:2:0, the Annex K.1 tables under the IJG quality rule, the
+// Annex K.3 Huffman tables, edge pixels repeated into partial MCUs.  The host encoder takes from here the constants, the tables, the header
+// bytes, the colour conversion, the 1-D DCT, the quantiser and the run-length coder; its own are the order of its DCT passes, its 64-bit bit
+// writer and its threads (kbe_jpeg.cpp).  The device encoder adds RESTART INTERVALS: a DRI segment declares intervals of kRestartMcus MCUs;
+// every interval starts on a byte boundary with the DC predictors at 0, ends padded with 1-bits and is followed by RSTm, m = 0..7 in turn
+// (none after the last).  Intervals are then independent: the unit of work of the kernels.
 //
 // Every fp32 operation here is one IEEE add, sub or mul (no contraction: -ffp-contract=off on both compilers), every conversion exact.
 #pragma once
@@ -68,6 +71,8 @@ KBE_MJ_HD size_t stream_bound(int W, int H)
 KBE_MJ_HD float luma(float r, float g, float b) { return 0.299f * r + 0.587f * g + 0.114f * b - 128.0f; }
 KBE_MJ_HD float chroma_b(float r, float g, float b) { return -0.168735892f * r - 0.331264108f * g + 0.5f * b; }
 KBE_MJ_HD float chroma_r(float r, float g, float b) { return 0.5f * r - 0.418687589f * g - 0.081312411f * b; }
+// a chroma sample: the 2 x 2 pixels under it, top left, top right, bottom left, bottom right
+KBE_MJ_HD float average4(float a, float b, float c, float d) { return 0.25f * (a + b + c + d); }
 
 // component 0..3: the MCU's four luma blocks, 4: Cb, 5: Cr, of one pixel (x, y clamped to the image: edge pixels repeat)
 KBE_MJ_HD float sample(const uint8_t* frame, const Geometry& g, int x, int y, int comp)
@@ -88,25 +93,27 @@ KBE_MJ_HD void block_row(const uint8_t* frame, const Geometry& g, int mx, int my
     } else {
         const int y = my * 16 + 2 * r, x0 = mx * 16;
         for (int j = 0; j < 8; j++)
-            v[j] = 0.25f * (sample(frame, g, x0 + 2 * j, y, comp) + sample(frame, g, x0 + 2 * j + 1, y, comp) + sample(frame, g, x0 + 2 * j, y + 1, comp) +
+            v[j] = average4(sample(frame, g, x0 + 2 * j, y, comp), sample(frame, g, x0 + 2 * j + 1, y, comp), sample(frame, g, x0 + 2 * j, y + 1, comp),
                             sample(frame, g, x0 + 2 * j + 1, y + 1, comp));
     }
 }
 
 // ---------------------------------------------------------------------------------------
-// the Arai-Agui-Nakajima forward DCT of eight values, in place; outputs scaled by the factors folded into Tables::rq
+// the Arai-Agui-Nakajima forward DCT of eight values, in place; outputs scaled by the factors folded into Tables::rq.  V: float (the
+// kernels, the twin), or a vector of floats that takes as many transforms side by side (the host encoder: the eight columns of a block)
 // ---------------------------------------------------------------------------------------
-KBE_MJ_HD void fdct8(float d[8])
+template <class V>
+KBE_MJ_HD void fdct8(V d[8])
 {
-    const float t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
-    const float t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
-    const float t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    const V t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
+    const V t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+    const V t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
     d[0] = t10 + t11; d[4] = t10 - t11;
-    const float z1 = (t12 + t13) * 0.707106781f;
+    const V z1 = (t12 + t13) * 0.707106781f;
     d[2] = t13 + z1; d[6] = t13 - z1;
-    const float u10 = t4 + t5, u11 = t5 + t6, u12 = t6 + t7;
-    const float z5 = (u10 - u12) * 0.382683433f, z2 = 0.541196100f * u10 + z5, z4 = 1.306562965f * u12 + z5, z3 = u11 * 0.707106781f;
-    const float z11 = t7 + z3, z13 = t7 - z3;
+    const V u10 = t4 + t5, u11 = t5 + t6, u12 = t6 + t7;
+    const V z5 = (u10 - u12) * 0.382683433f, z2 = 0.541196100f * u10 + z5, z4 = 1.306562965f * u12 + z5, z3 = u11 * 0.707106781f;
+    const V z11 = t7 + z3, z13 = t7 - z3;
     d[5] = z13 + z2; d[3] = z13 - z2; d[1] = z11 + z4; d[7] = z11 - z4;
 }
 
@@ -325,8 +332,11 @@ struct HeaderWriter {
     }
 };
 
-// quality 1..100 (clamped): the IJG rule (jpeg_quality_scaling) on the Annex K.1 tables; the reciprocals in double, rounded once
-inline void tables_build(int W, int H, int quality, Tables* t)
+// quality 1..100 (clamped): the IJG rule (jpeg_quality_scaling) on the Annex K.1 tables; the reciprocals in double, rounded once.
+// restart_mcus: what the DRI segment declares -- kRestartMcus for the device encoder's stream (kHeaderBytes of header; the default, so that
+// a caller that knows nothing of the host encoder reads as it did), 0 for a stream without intervals and without the segment (the host
+// encoder's).  -> the header's length
+inline int tables_build(int W, int H, int quality, Tables* t, int restart_mcus = kRestartMcus)
 {
     static const double aan[8] = { 1.0, 1.387039845, 1.306562965, 1.175875602, 1.0, 0.785694958, 0.541196100, 0.275899379 };
     if (quality < 1) quality = 1;
@@ -375,9 +385,9 @@ inline void tables_build(int W, int H, int quality, Tables* t)
             hw.marker(0xC4, body, 17 + dht[k].n);
         }
     }
-    { const uint8_t dri[2] = { (uint8_t) (kRestartMcus >> 8), (uint8_t) kRestartMcus }; hw.marker(0xDD, dri, 2); }       // DRI
+    if (restart_mcus) { const uint8_t dri[2] = { (uint8_t) (restart_mcus >> 8), (uint8_t) restart_mcus }; hw.marker(0xDD, dri, 2); }        // DRI
     { static const uint8_t sos[10] = { 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0 }; hw.marker(0xDA, sos, 10); }
-    // (hw.p - t->header == kHeaderBytes: tests/mjpeg_check.cpp asserts it)
+    return (int) (hw.p - t->header);            // (kHeaderBytes with intervals: tests/mjpeg_check.cpp asserts it)
 }
 
 // The definition of a frame's stream: the pieces above, one after the other.

@@ -2,6 +2,7 @@
 JPEG encoder the Motion-JPEG video writers use, a batch of frames on host threads (include/kbe_jpeg.h) -- against Pillow, and the PNG
 writer (zlib directly).  Pillow is the CHECKER here (its decoder reads every stream; its encoder's tables and quality are the bar)."""
 import ctypes
+import hashlib
 import io
 import os
 import re
@@ -147,6 +148,59 @@ def test_a_batch_on_threads_equals_the_frames_one_by_one(lib):
         for i, f in enumerate(frames):
             assert outs[i][:sizes[i]].tobytes() == encode(lib, f, 92)[1], 'frame %d on %d threads' % (i, threads)
     assert lib.kbe_jpeg_encode_batch(None, 0, w, h, 3 * w, 92, None, ctypes.c_size_t(cap), None, 4) == 0      # an empty batch is no error
+
+
+PIN_SIZES = [(1, 1), (16, 17), (17, 16), (50, 37), (3, 200), (96, 128)]
+PIN_QUALITIES = [1, 10, 50, 75, 92, 100]
+PINNED_SHA256 = '619d75e7b17c59f0cd10389a221ed1fe86eeca6aebfb651f9ff65835e58bed2e'
+
+
+def pin_corpus():
+    """(frame, quality) of the byte pin, from integers alone (no sin, no normal: nothing a libm could round differently): noise, a ramp
+    that runs through every value along both axes, a flat frame; every size at every quality."""
+    for k, (h, w) in enumerate(PIN_SIZES):
+        yy, xx = np.mgrid[0:h, 0:w]
+        ramp = ((7 * xx + 3 * yy)[:, :, None] + np.array([0, 85, 170])) % 256
+        for quality in PIN_QUALITIES:
+            yield np.random.default_rng(100 * k + quality).integers(0, 256, (h, w, 3), dtype=np.uint8), quality
+            yield ramp.astype(np.uint8), quality
+            yield np.full((h, w, 3), (41 * k + quality) % 256, np.uint8), quality
+
+
+def pin_digest(lib):
+    digest = hashlib.sha256()
+    for frame, quality in pin_corpus():
+        rc, data = encode(lib, frame, quality)
+        assert rc == 0
+        digest.update(struct.pack('<I', len(data)) + data)
+    return digest.hexdigest()
+
+
+def test_the_host_encoders_bytes_are_pinned(lib):
+    """The streams of 108 integer-made frames (pin_corpus), each behind its length, hashed in order.  PINNED_SHA256 was recorded from the
+    library of the commit BEFORE the host encoder moved onto csrc/kbe_mjpeg_block.h (that commit's tree exported with `git archive` and built
+    on its own), not from the tree under test: the move changed no byte, and an edit that changes one has to change this constant and say why."""
+    assert pin_digest(lib) == PINNED_SHA256
+
+
+HOST_DEVICE_SIZES = [(96, 128), (50, 37), (17, 16), (1, 1), (64, 80), (256, 256)]
+
+
+@pytest.mark.parametrize('size', HOST_DEVICE_SIZES)
+def test_host_and_device_streams_decode_to_the_same_picture(lib, size):
+    """The host library's stream and the device encoder's (its CPU twin's, mjpeg_cases.twin: restart intervals, another bit writer) of the same
+    frame share one definition of the picture: decoded by Pillow they are equal arrays, on a photo-like and a noise frame at four qualities.
+    The two take the DCT's passes in different orders (host: columns, then rows, eight side by side; device: rows, then columns), so a
+    coefficient that lies on a rounding tie of the quantiser within the last bit may legitimately differ on some future input: this test pins
+    THESE inputs, on which the two agreed in every pixel before the definition was shared, not all inputs."""
+    import mjpeg_cases as mc
+    h, w = size
+    for frame in (photo_like(h, w, 3), np.random.default_rng(1).integers(0, 256, (h, w, 3), dtype=np.uint8)):
+        for quality in (10, 50, 92, 100):
+            rc, host = encode(lib, frame, quality)
+            assert rc == 0
+            device = mc.twin(frame[None], quality)[0][0]
+            assert np.array_equal(decode(host), decode(device)), '%dx%d at quality %d' % (h, w, quality)
 
 
 def test_errors_are_codes(lib):
