@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define KBE_ABI_VERSION 12
+#define KBE_ABI_VERSION 13
 
 /* the library is built with -fvisibility=hidden; only these entry points are exported */
 #if defined(__GNUC__)
@@ -519,6 +519,31 @@ KBE_API size_t kbe_mjpeg_bound(int W, int H);
 KBE_API size_t kbe_mjpeg_scratch_bytes(int W, int H, int n_frames);
 KBE_API int kbe_mjpeg_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H, int stride_bytes, int quality, int flags,
                              void* scratch, uint8_t* streams, size_t cap, uint64_t* offsets, int* status, kbe_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * PNG frames on the device: frames that lie in HBM leave as the PNG files of --write-frames (pipeline.write_frames), lossless: a file
+ * decodes to the frame's own bytes.
+ *
+ * The file: signature, IHDR (8 bits, colour type 2, no interlace), ONE IDAT, IEND.  The IDAT's zlib stream carries the rows filtered with
+ * Sub (what pipeline.png_bytes compresses) in independent segments of 16384 bytes -- the units of work of the kernels: runs of equal
+ * bytes as distance-1 matches, one dynamic-Huffman block per segment followed by an empty stored block that restores the byte boundary, or
+ * the segment as a stored block where that is not longer.  The file is defined byte for byte by csrc/kbe_png_block.h executed serially
+ * on a CPU (tests/png_check.cpp).
+ *
+ * kbe_png_encode: frames_u8 = HOST array of n_frames DEVICE pointers to [H][stride_bytes] rows of 3-byte pixels (R, G, B; B, G, R with
+ * KBE_PNG_BGR: the file holds R, G, B either way); W, H <= 65535 and kbe_png_bound(W, H) != 0; any n_frames >= 1 (the entry cuts them
+ * into launches).  Frame i's file is files[offsets[i] .. offsets[i + 1]), the files back to back; offsets: DEVICE [n_frames + 1], 8-byte
+ * aligned.  If the files need more than `cap` bytes, *status (DEVICE) is 1, the offsets still hold the true sizes and no byte at or beyond
+ * cap is written; else 0.  kbe_png_bound: bytes that hold ANY W x H frame's file (every segment stored: noise reaches it); 0 for a size
+ * the entry refuses (a file of 2^31 bytes or more).  scratch: kbe_png_scratch_bytes(W, H, n_frames) bytes, 8-byte aligned, contents
+ * irrelevant: 24 bytes per segment of at most 12 frames -- it does not grow with the files.  Every argument is validated before anything
+ * is enqueued; nothing is allocated; all launches are asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------- */
+#define KBE_PNG_BGR 1
+KBE_API size_t kbe_png_bound(int W, int H);
+KBE_API size_t kbe_png_scratch_bytes(int W, int H, int n_frames);
+KBE_API int kbe_png_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H, int stride_bytes, int flags, void* scratch,
+                           uint8_t* files, size_t cap, uint64_t* offsets, int* status, kbe_stream_t stream);
 
 #ifdef __cplusplus
 }

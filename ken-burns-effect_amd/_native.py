@@ -30,11 +30,13 @@ SYMBOLS = (
     'kbe_frame_scratch_bytes', 'kbe_frame_scratch_init', 'kbe_render_frame', 'kbe_render_frame_stages', 'kbe_render_frame_group', 'kbe_cloud_pack_bytes', 'kbe_cloud_pack', 'kbe_render_frame_fused', 'kbe_render_frame_group_fused', 'kbe_render_frame_group_ahead_ok', 'kbe_render_frame_group_ahead', 'kbe_video_scratch_stride', 'kbe_video_stage_bytes', 'kbe_render_video', 'kbe_render_pointcloud_tiled', 'kbe_generate_mask', 'kbe_frame_u8', 'kbe_crop_resize_u8', 'kbe_depth_to_points', 'kbe_shift_points',
     'kbe_spatial_filter', 'kbe_laplacian_valid', 'kbe_pconv_epilogue', 'kbe_prelu_mask', 'kbe_bias_act', 'kbe_upsample2x_act', 'kbe_frame_scratch_init_sets', 'kbe_video_handoff_status',
     'kbe_mjpeg_bound', 'kbe_mjpeg_scratch_bytes', 'kbe_mjpeg_encode',
+    'kbe_png_bound', 'kbe_png_scratch_bytes', 'kbe_png_encode',
 )
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_LANES = 8          # KBE_MAX_LANES
 KBE_MJPEG_BGR = 1      # kbe_mjpeg_encode flags
+KBE_PNG_BGR = 1        # kbe_png_encode flags
 DEFAULT_LANES = 4      # streams the frame loop spreads consecutive frames over (env KBE_LANES)
 FUSED_MAX_DENSITY = 20.0         # clouds up to this many points per pixel take the fused scatter by default (KBE_FUSED=auto).  Round 5: a tile's candidate list holds 2048
                                  # sub-blocks (512 before: the densest tiles' lists overflowed from 5 points per pixel on and those tiles scanned the cloud) and a record
@@ -114,6 +116,8 @@ def load():
     lib.kbe_cloud_pack_bytes.restype = ctypes.c_size_t
     lib.kbe_mjpeg_bound.restype = ctypes.c_size_t
     lib.kbe_mjpeg_scratch_bytes.restype = ctypes.c_size_t
+    lib.kbe_png_bound.restype = ctypes.c_size_t
+    lib.kbe_png_scratch_bytes.restype = ctypes.c_size_t
     if lib.kbe_abi_version() != ABI_VERSION:
         raise KbeError('libkbe_hip.so ABI %d != expected %d' % (lib.kbe_abi_version(), ABI_VERSION))
     _lib = lib
@@ -743,6 +747,37 @@ class HipKernels:
                 raise KbeError('kbe_mjpeg_encode: %d bytes do not fit a buffer of %d' % (offsets[n], cap))
             cap = offsets[n]
         data = streams[:offsets[n]].cpu().numpy()
+        return [data[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
+
+    # -- PNG frames on the device ----------------------------------------------------------
+    def png_encode(self, frames, bgr=False, cap=None):
+        """uint8 [n,H,W,3] frames in HBM -> one PNG file (bytes) per frame, encoded on the device (kbe_png_encode): lossless, a file decodes
+        to its frame.  ``bgr``: the frames hold B, G, R (what Pipeline renders from a cv2.imread image); the files hold R, G, B either way.
+        One synchronisation for the offsets and the status word, then exactly offsets[n] bytes are copied.  ``cap``: the files' buffer
+        (default: the raw size of the frames plus a kilobyte per frame -- only noise needs more); when the files do not fit, the call is
+        repeated once with a buffer of the true size, which the first run has reported."""
+        if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.size(3) == 3 and frames.size(0) >= 1):
+            raise KbeError('png_encode takes a uint8 [n,H,W,3] tensor on the GPU')
+        n, H, W, _ = frames.shape
+        base, step = _ptr(frames, torch.uint8).value, H * W * 3
+        pointers = (ctypes.c_void_p * n)(*[base + i * step for i in range(n)])
+        device = frames.device
+        scratch = torch.empty((int(self.lib.kbe_png_scratch_bytes(_i(W), _i(H), _i(n))) + 7) // 8 + 1, dtype=torch.int64, device=device)
+        meta = torch.empty(n + 2, dtype=torch.int64, device=device)          # offsets [n + 1], then the status word
+        status = ctypes.c_void_p(meta.data_ptr() + 8 * (n + 1))
+        cap = int(cap) if cap is not None else n * (1024 + step)
+        for attempt in (0, 1):
+            files = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+            self._check(self.lib.kbe_png_encode(pointers, _i(n), _i(W), _i(H), _i(3 * W), _i(KBE_PNG_BGR if bgr else 0), _ptr(scratch, torch.int64),
+                                                _ptr(files, torch.uint8), _z(cap), _ptr(meta, torch.int64), status, _stream()), 'kbe_png_encode')
+            host = meta.cpu()                                               # (the one synchronisation)
+            offsets, overflow = host[:n + 1].tolist(), int(host[n + 1].item()) & 0xFFFFFFFF
+            if not overflow:
+                break
+            if attempt == 1:
+                raise KbeError('kbe_png_encode: %d bytes do not fit a buffer of %d' % (offsets[n], cap))
+            cap = offsets[n]
+        data = files[:offsets[n]].cpu().numpy()
         return [data[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
 
     # -- torch glue ---------------------------------------------------------------------

@@ -7,12 +7,13 @@
 //      eight lanes per block (rows in registers, transpose through LDS, columns), quantisation into LDS; then one lane per BLOCK packs the
 //      block's Huffman codes and value bits into words of its own in LDS, and one lane per interval sends them on, in order, into a sink
 //      that counts the stream's bytes (stuffed 0xFF, padding, RSTm): the interval's LENGTH is all that is stored;
-//   2. an exclusive scan of the lengths over all intervals of all frames of the launch (sums of 256, a scan of the sums, apply): every
+//   2. an exclusive scan of the lengths over all intervals of all frames of the launch (kbe_units_scan.h: sums of 256, a scan of the sums, apply): every
 //      interval's place, every frame's offsets[i], the total and `status`;
 //   3. k_mjpeg_encode<true>: the same code again, the sink now storing the bytes at their place (nothing at or beyond `cap`).
 // No kernel waits for another workgroup.  n frames are cut into launches of kFramesPerLaunch.
 #include "kbe_host.h"
 #include "kbe_mjpeg_block.h"
+#include "kbe_units_scan.h"
 
 using namespace kbe;
 using namespace kbe_mjpeg;
@@ -24,8 +25,6 @@ constexpr int kGroupIntervals = 4;                                              
 constexpr int kGroupBlocks = kGroupIntervals * kRestartMcus * 6;                // 96 blocks
 constexpr int kEncodeThreads = 64 * kGroupIntervals;
 constexpr int kBlocksAtOnce = kEncodeThreads / 8;                               // eight lanes per block
-constexpr int kScanThreads = 256;                                               // intervals per workgroup of the scan
-constexpr int kSumsThreads = 64;                                                // sums the scan of the sums takes at once
 static_assert(kGroupBlocks % kBlocksAtOnce == 0, "the DCT loop takes whole rounds");
 
 struct EncodeArgs {
@@ -158,67 +157,6 @@ __global__ __launch_bounds__(kEncodeThreads) void k_mjpeg_encode(const EncodeArg
     }
 }
 
-// exclusive scan of one value per thread over a workgroup of THREADS; *total: the sum
-template <int THREADS>
-__device__ __forceinline__ uint64_t group_exclusive_scan(uint64_t v, uint64_t* lds, uint64_t* total)
-{
-    const int t = (int) threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int d = 1; d < THREADS; d <<= 1) {
-        const uint64_t below = t >= d ? lds[t - d] : 0;
-        __syncthreads();
-        lds[t] += below;
-        __syncthreads();
-    }
-    const uint64_t inclusive = lds[t];
-    *total = lds[THREADS - 1];
-    __syncthreads();
-    return inclusive - v;
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_mjpeg_sums(const uint32_t* __restrict__ counts, size_t n, uint64_t* __restrict__ sums)
-{
-    __shared__ uint64_t lds[kScanThreads];
-    const size_t at = (size_t) blockIdx.x * kScanThreads + threadIdx.x;
-    uint64_t total;
-    group_exclusive_scan<kScanThreads>(at < n ? counts[at] : 0u, lds, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one workgroup: the sums become where their kScanThreads intervals start; offsets[f0] carries on from the launch before; the total and `status`
-__global__ __launch_bounds__(kSumsThreads) void k_mjpeg_scan_sums(uint64_t* __restrict__ sums, size_t n_sums, uint64_t* __restrict__ offsets, int f0, int nf, uint64_t cap,
-                                                                  int* __restrict__ status)
-{
-    __shared__ uint64_t lds[kSumsThreads];
-    uint64_t carry = f0 == 0 ? 0 : offsets[f0];
-    for (size_t at = 0; at < n_sums; at += kSumsThreads) {
-        const size_t i = at + threadIdx.x;
-        const uint64_t mine = i < n_sums ? sums[i] : 0;
-        uint64_t total;
-        const uint64_t before = group_exclusive_scan<kSumsThreads>(mine, lds, &total);
-        if (i < n_sums) sums[i] = carry + before;
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        offsets[f0 + nf] = carry;
-        *status = carry > cap ? 1 : 0;              // (the totals grow from launch to launch: the last launch's word is the call's)
-    }
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_mjpeg_starts(const uint32_t* __restrict__ counts, size_t n, const uint64_t* __restrict__ sums, int intervals,
-                                                               uint64_t* __restrict__ starts, uint64_t* __restrict__ offsets, int f0)
-{
-    __shared__ uint64_t lds[kScanThreads];
-    const size_t at = (size_t) blockIdx.x * kScanThreads + threadIdx.x;
-    uint64_t total;
-    const uint64_t start = sums[blockIdx.x] + group_exclusive_scan<kScanThreads>(at < n ? counts[at] : 0u, lds, &total);
-    if (at < n) {
-        starts[at] = start;
-        if (at % (size_t) intervals == 0) offsets[f0 + at / (size_t) intervals] = start;       // a frame's first interval: where its stream starts
-    }
-}
-
 struct ScratchLayout { size_t counts, starts, sums, bytes; };       // byte offsets
 
 ScratchLayout scratch_layout(int W, int H, int n_frames)
@@ -270,9 +208,9 @@ int kbe_mjpeg_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H
         for (int i = 0; i < kFramesPerLaunch; i++) a.frames[i] = i < nf ? frames_u8[f0 + i] : nullptr;
         const size_t n = (size_t) nf * (size_t) a.g.intervals, n_sums = (n + kScanThreads - 1) / kScanThreads;
         hipLaunchKernelGGL(k_mjpeg_encode<false>, dim3(groups, (unsigned) nf), dim3(kEncodeThreads), 0, s, a, counts, (const uint64_t*) starts, streams, (uint64_t) cap);
-        hipLaunchKernelGGL(k_mjpeg_sums, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, sums);
-        hipLaunchKernelGGL(k_mjpeg_scan_sums, dim3(1), dim3(kSumsThreads), 0, s, sums, n_sums, offsets, f0, nf, (uint64_t) cap, status);
-        hipLaunchKernelGGL(k_mjpeg_starts, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, (const uint64_t*) sums, a.g.intervals, starts, offsets, f0);
+        hipLaunchKernelGGL(k_units_sums, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, sums);
+        hipLaunchKernelGGL(k_units_scan_sums, dim3(1), dim3(kSumsThreads), 0, s, sums, n_sums, offsets, f0, nf, (uint64_t) cap, status);
+        hipLaunchKernelGGL(k_units_starts, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, (const uint64_t*) sums, a.g.intervals, starts, offsets, f0);
         hipLaunchKernelGGL(k_mjpeg_encode<true>, dim3(groups, (unsigned) nf), dim3(kEncodeThreads), 0, s, a, counts, (const uint64_t*) starts, streams, (uint64_t) cap);
         const int rc = launched("kbe_mjpeg_encode");
         if (rc != KBE_OK) return rc;

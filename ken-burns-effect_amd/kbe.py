@@ -6,6 +6,7 @@
         [--semantics-path vgg19_bn_state_dict.pth]     (new: the reference downloads these weights through torchvision)
         [--allow-random-weights]                       (new: render with seeded weights where a checkpoint is missing instead of failing)
         [--jpeg native|pillow|device]                  (new: who encodes a Motion-JPEG video's frames -- host threads, Pillow, or the GPU: env KBE_JPEG)
+        [--png native|device]                          (new: who encodes the PNG frames of --write-frames -- host threads or the GPU: env KBE_PNG)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -18,12 +19,12 @@ import numpy as np
 import torch
 
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
-                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=']
+                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=']
 
 
 def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
-           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None,
+           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -36,6 +37,8 @@ def parse(argv):
             cfg[name] = True
         elif argument != '':
             cfg[name] = argument
+    if cfg['png'] not in (None, 'native', 'device'):
+        raise SystemExit('--png %s: native or device' % cfg['png'])
     return cfg, window
 
 
@@ -86,6 +89,9 @@ def main(argv=None):
             raise SystemExit('--jpeg %s: native, pillow or device' % cfg['jpeg'])
         import os
         os.environ['KBE_JPEG'] = cfg['jpeg']        # (the writers read the switch where they encode: pipeline.jpeg_encoder)
+    if cfg['png'] is not None:
+        import os
+        os.environ['KBE_PNG'] = cfg['png']          # (... and pipeline.png_encoder)
     image = load_image(cfg['in'], cfg['pretrained-estim'])
     zoom = windows_for(image.shape[3], image.shape[2], window, cfg['dolly'])
     paths = [cfg['estim-path'], cfg['refine-path'], cfg['inpaint-path']] + ([cfg['inpaint-depth']] if cfg['inpaint-depth'] else [])

@@ -135,19 +135,32 @@ class Pipeline():
             if inpaint_depth:
                 raise NotImplementedError('two-network depth inpainting is broken in the reference (common.py:50-69)')
             # KBE_JPEG=device, a Motion-JPEG video (no ffmpeg binary) and no PNG frames: the frames stay in HBM, the GPU encodes them and the
-            # streams come to the host, a tenth of the pixels' bytes; any other combination takes the host route below
-            on_device = output_path is not None and not self.output_frames and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
+            # streams come to the host, a tenth of the pixels' bytes.  KBE_PNG=device and PNG frames asked for: the frames stay in HBM as
+            # well and the GPU encodes the PNG files (png_encoder); the video then comes from the same frames in HBM if the first
+            # condition holds but for the PNG frames, and from the frames fetched raw otherwise.  Any other combination takes the host
+            # route below
+            jpeg_on_device = output_path is not None and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
+            png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
+            on_device = png_on_device or (jpeg_on_device and not self.output_frames)
             frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                               'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                               'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device)
         if on_device:
             os.makedirs(output_path, exist_ok=True)
-            # (the frames are in the INPUT's channel order, as below: the encoder reads B, G, R unless --pretrained-estim)
-            encoded = jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=not pretrained_estim)
-            # forth and back (:131): every distinct frame was encoded once, the way back is the same byte objects again
-            write_video(os.path.join(output_path, '3d_kbe.mp4'), None, fps=25, jpegs=encoded + encoded[-2::-1], frame_size=tuple(frames.shape[1:3]))
-            host = frames.cpu().numpy()                                                 # the return value, fetched after the video is written
-            return [host[i] for i in range(host.shape[0])]
+            # (the frames are in the INPUT's channel order, as below: the encoders read B, G, R unless --pretrained-estim)
+            if png_on_device:
+                from . import _native
+                write_frames(os.path.join(output_path, 'frames'), None, pngs=_native.kernels().png_encode(frames, bgr=not pretrained_estim))
+            if jpeg_on_device:
+                encoded = jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=not pretrained_estim)
+                # forth and back (:131): every distinct frame was encoded once, the way back is the same byte objects again
+                write_video(os.path.join(output_path, '3d_kbe.mp4'), None, fps=25, jpegs=encoded + encoded[-2::-1], frame_size=tuple(frames.shape[1:3]))
+            host = frames.cpu().numpy()                                                 # the return value (with jpeg_on_device: fetched after the video is written)
+            out = [host[i] for i in range(host.shape[0])]
+            if not jpeg_on_device:
+                rgb = out if pretrained_estim else [f[:, :, ::-1] for f in out]
+                write_video(os.path.join(output_path, '3d_kbe.mp4'), rgb + rgb[-2::-1], fps=25)
+            return out
         if output_path is not None:
             os.makedirs(output_path, exist_ok=True)
             # channel order on disk as the reference produces it: frames are in the INPUT's channel order
@@ -226,15 +239,26 @@ def png_bytes(frame_rgb, level=1):
     return (b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0)) + chunk(b'IDAT', zlib.compress(raw.tobytes(), level)) + chunk(b'IEND', b''))
 
 
-def write_frames(frames_dir, frames_rgb):
-    """%d.png per frame (pipeline.py:122-126), encoded on the writers' threads."""
+def png_encoder():
+    """Who encodes the PNG frames of --write-frames: 'native' (png_bytes on the writers' host threads, the default) or 'device' (env
+    KBE_PNG=device, kbe.py --png device: the GPU encodes frames that stay in HBM -- kbe_png_encode, include/kbe.h --, opt-in; the files are
+    lossless either way, their bytes differ).  No fallback: without the HIP library the device route raises."""
+    kind = os.environ.get('KBE_PNG', 'native')
+    if kind not in ('native', 'device'):
+        raise ValueError('KBE_PNG=%s: native or device' % kind)
+    return kind
+
+
+def write_frames(frames_dir, frames_rgb, pngs=None):
+    """%d.png per frame (pipeline.py:122-126), encoded on the writers' threads.  ``pngs``: files that are encoded already (one bytes object
+    per frame: HipKernels.png_encode); frames_rgb is then not looked at and the writers' threads only write."""
     os.makedirs(frames_dir, exist_ok=True)
 
     def save(job):
         idx, frame = job
         with open(os.path.join(frames_dir, '%d.png' % idx), 'wb') as f:
-            f.write(png_bytes(frame))
-    _on_threads(list(enumerate(frames_rgb)), save)
+            f.write(frame if pngs is not None else png_bytes(frame))
+    _on_threads(list(enumerate(pngs if pngs is not None else frames_rgb)), save)
 
 
 def _encoded(frames_rgb, quality, jpegs, frame_size):
