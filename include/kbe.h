@@ -498,21 +498,27 @@ KBE_API int kbe_bias_act(const float* x, const float* bias, const float* slope, 
 KBE_API int kbe_upsample2x_act(const float* x, const float* slope, int B, int C, int H, int W, float* out, kbe_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * Motion-JPEG on the device: frames that lie in HBM (kbe_render_video with host_out = device memory, common.render_frames with
- * keep_on_device) leave as baseline JPEG streams -- about a tenth of the bytes -- for the video writers (pipeline.write_mjpeg_mp4 / _avi).
+ * Encoders on the device: frames that lie in HBM (kbe_render_video with host_out = device memory, common.render_frames with
+ * keep_on_device) leave as encoded streams or files instead of pixels.  kbe_mjpeg_encode and kbe_png_encode share ONE contract
+ * (E stands for kbe_mjpeg or kbe_png, "unit" for a frame's stream or file):
+ *   frames_u8: HOST array of n_frames DEVICE pointers to [H][stride_bytes] rows of 3-byte pixels (R, G, B; B, G, R with the entry's _BGR
+ *              flag), stride_bytes >= 3 W; W, H <= 65535; any n_frames >= 1 -- the entry cuts them into launches of at most 12 frames;
+ *   out (streams, files), cap: frame i's unit is out[offsets[i] .. offsets[i + 1]), the units back to back; NO byte at or beyond cap is
+ *              written (out may be NULL when cap is 0);
+ *   offsets:   DEVICE [n_frames + 1], 8-byte aligned: the TRUE sizes, whether they fit or not;
+ *   status:    DEVICE int: 1 if the units need more than cap bytes (run again with a buffer of offsets[n_frames] bytes), else 0;
+ *   scratch:   E_scratch_bytes(W, H, n_frames) bytes, 8-byte aligned, contents irrelevant: some bytes per unit of work of at most 12 frames --
+ *              it grows neither past one launch's frames nor with the output;
+ *   E_bound(W, H): bytes that hold ANY W x H frame's unit; 0 for a size the entry refuses.
+ * Every argument is validated before anything is enqueued (KBE_E_INVALID, kbe_last_error names the entry and the argument); nothing is
+ * allocated; all launches are asynchronous on `stream`.
  *
- * The picture is the one libkbe_jpeg.so writes (baseline sequential DCT, 8 bits, JFIF YCbCr 4:2:0, the Annex K.1 tables under the IJG
- * quality rule, the Annex K.3 Huffman tables, edge pixels repeated into partial MCUs) with RESTART INTERVALS: a DRI segment, every
+ * Motion-JPEG (kbe_mjpeg_encode): baseline JPEG streams -- about a tenth of the bytes -- for the video writers (pipeline.write_mjpeg_mp4 /
+ * _avi).  The picture is the one libkbe_jpeg.so writes (baseline sequential DCT, 8 bits, JFIF YCbCr 4:2:0, the Annex K.1 tables under the
+ * IJG quality rule, the Annex K.3 Huffman tables, edge pixels repeated into partial MCUs) with RESTART INTERVALS: a DRI segment, every
  * interval byte-aligned with its DC predictors at 0 and followed by RSTm -- the independent units of work of the kernels.  The stream is
- * defined byte for byte by csrc/kbe_mjpeg_block.h executed serially on a CPU (tests/mjpeg_check.cpp).
- *
- * kbe_mjpeg_encode: frames_u8 = HOST array of n_frames DEVICE pointers to [H][stride_bytes] rows of 3-byte pixels (R, G, B; B, G, R with
- * KBE_MJPEG_BGR); quality 1..100; W, H <= 65535; any n_frames >= 1 (the entry cuts them into launches).  Frame i's stream is
- * streams[offsets[i] .. offsets[i + 1]), the streams back to back; offsets: DEVICE [n_frames + 1], 8-byte aligned.  If the streams need more
- * than `cap` bytes, *status (DEVICE) is 1, the offsets still hold the true sizes and no byte at or beyond cap is written; else 0.
- * kbe_mjpeg_bound: bytes that hold ANY W x H frame's stream (the true worst case).  scratch: kbe_mjpeg_scratch_bytes(W, H, n_frames)
- * bytes, 8-byte aligned, contents irrelevant: 12 bytes per restart interval of at most 12 frames -- it does not grow with the streams.
- * Every argument is validated before anything is enqueued; nothing is allocated; all launches are asynchronous on `stream`.
+ * defined byte for byte by csrc/kbe_mjpeg_block.h executed serially on a CPU (tests/mjpeg_check.cpp).  quality 1..100.  kbe_mjpeg_bound is
+ * the true worst case.  Scratch: 12 bytes per restart interval.
  * ------------------------------------------------------------------------------------- */
 #define KBE_MJPEG_BGR 1
 KBE_API size_t kbe_mjpeg_bound(int W, int H);
@@ -520,25 +526,13 @@ KBE_API size_t kbe_mjpeg_scratch_bytes(int W, int H, int n_frames);
 KBE_API int kbe_mjpeg_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H, int stride_bytes, int quality, int flags,
                              void* scratch, uint8_t* streams, size_t cap, uint64_t* offsets, int* status, kbe_stream_t stream);
 
-/* ---------------------------------------------------------------------------------------
- * PNG frames on the device: frames that lie in HBM leave as the PNG files of --write-frames (pipeline.write_frames), lossless: a file
- * decodes to the frame's own bytes.
- *
- * The file: signature, IHDR (8 bits, colour type 2, no interlace), ONE IDAT, IEND.  The IDAT's zlib stream carries the rows filtered with
- * Sub (what pipeline.png_bytes compresses) in independent segments of 16384 bytes -- the units of work of the kernels: runs of equal
- * bytes as distance-1 matches, one dynamic-Huffman block per segment followed by an empty stored block that restores the byte boundary, or
- * the segment as a stored block where that is not longer.  The file is defined byte for byte by csrc/kbe_png_block.h executed serially
- * on a CPU (tests/png_check.cpp).
- *
- * kbe_png_encode: frames_u8 = HOST array of n_frames DEVICE pointers to [H][stride_bytes] rows of 3-byte pixels (R, G, B; B, G, R with
- * KBE_PNG_BGR: the file holds R, G, B either way); W, H <= 65535 and kbe_png_bound(W, H) != 0; any n_frames >= 1 (the entry cuts them
- * into launches).  Frame i's file is files[offsets[i] .. offsets[i + 1]), the files back to back; offsets: DEVICE [n_frames + 1], 8-byte
- * aligned.  If the files need more than `cap` bytes, *status (DEVICE) is 1, the offsets still hold the true sizes and no byte at or beyond
- * cap is written; else 0.  kbe_png_bound: bytes that hold ANY W x H frame's file (every segment stored: noise reaches it); 0 for a size
- * the entry refuses (a file of 2^31 bytes or more).  scratch: kbe_png_scratch_bytes(W, H, n_frames) bytes, 8-byte aligned, contents
- * irrelevant: 24 bytes per segment of at most 12 frames -- it does not grow with the files.  Every argument is validated before anything
- * is enqueued; nothing is allocated; all launches are asynchronous on `stream`.
- * ------------------------------------------------------------------------------------- */
+/* PNG (kbe_png_encode): the PNG files of --write-frames (pipeline.write_frames), lossless: a file decodes to the frame's own bytes (R, G, B in
+ * the file, whatever the flag says the frame holds).  The file: signature, IHDR (8 bits, colour type 2, no interlace), ONE IDAT, IEND.  The
+ * IDAT's zlib stream carries the rows filtered with Sub (what pipeline.png_bytes compresses) in independent segments of 16384 bytes -- the
+ * units of work of the kernels: runs of equal bytes as distance-1 matches, one dynamic-Huffman block per segment followed by an empty stored
+ * block that restores the byte boundary, or the segment as a stored block where that is not longer.  The file is defined byte for byte by
+ * csrc/kbe_png_block.h executed serially on a CPU (tests/png_check.cpp).  kbe_png_bound: every segment stored (noise reaches it); a frame
+ * whose file would have 2^31 bytes or more is refused: its bound is 0.  Scratch: 24 bytes per segment. */
 #define KBE_PNG_BGR 1
 KBE_API size_t kbe_png_bound(int W, int H);
 KBE_API size_t kbe_png_scratch_bytes(int W, int H, int n_frames);

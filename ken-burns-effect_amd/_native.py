@@ -718,67 +718,52 @@ class HipKernels:
                                                 _ptr(out, torch.uint8), _stream()), 'kbe_crop_resize_u8')
         return out
 
-    # -- Motion-JPEG on the device --------------------------------------------------------
+    # -- Motion-JPEG and PNG on the device -----------------------------------------------
+    def encode_raw(self, fmt, pointers, n, W, H, stride, own, scratch, out, cap, offsets, status):
+        """kbe_<fmt>_encode as it is (include/kbe.h, the encoders' common contract), on the current stream: addresses, not tensors; `own`: the
+        entry's integers between the stride and the scratch (the quality, the flags).  -> its return code."""
+        return getattr(self.lib, 'kbe_%s_encode' % fmt)(pointers, _i(n), _i(W), _i(H), _i(stride), *[_i(v) for v in own], ctypes.c_void_p(scratch), ctypes.c_void_p(out), _z(cap),
+                                                        ctypes.c_void_p(offsets), ctypes.c_void_p(status), _stream())
+
+    def _encode(self, fmt, frames, own, cap, first_guess):
+        """The whole of a tensor-level call of kbe_<fmt>_encode: -> the bytes of each frame."""
+        if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.size(3) == 3 and frames.size(0) >= 1):
+            raise KbeError('%s_encode takes a uint8 [n,H,W,3] tensor on the GPU' % fmt)
+        n, H, W, _ = frames.shape
+        base, step = _ptr(frames, torch.uint8).value, H * W * 3
+        pointers = (ctypes.c_void_p * n)(*[base + i * step for i in range(n)])
+        device = frames.device
+        scratch = torch.empty((int(getattr(self.lib, 'kbe_%s_scratch_bytes' % fmt)(_i(W), _i(H), _i(n))) + 7) // 8 + 1, dtype=torch.int64, device=device)
+        meta = torch.empty(n + 2, dtype=torch.int64, device=device)          # offsets [n + 1], then the status word
+        cap = int(cap) if cap is not None else first_guess(n, step)
+        for attempt in (0, 1):
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+            self._check(self.encode_raw(fmt, pointers, n, W, H, 3 * W, own, scratch.data_ptr(), out.data_ptr(), cap, meta.data_ptr(), meta.data_ptr() + 8 * (n + 1)), 'kbe_%s_encode' % fmt)
+            host = meta.cpu()                                               # (the one synchronisation)
+            offsets, overflow = host[:n + 1].tolist(), int(host[n + 1].item()) & 0xFFFFFFFF
+            if not overflow:
+                break
+            if attempt == 1:
+                raise KbeError('kbe_%s_encode: %d bytes do not fit a buffer of %d' % (fmt, offsets[n], cap))
+            cap = offsets[n]
+        data = out[:offsets[n]].cpu().numpy()
+        return [data[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
+
     def mjpeg_encode(self, frames, quality=92, bgr=False, cap=None):
         """uint8 [n,H,W,3] frames in HBM -> one baseline JPEG (bytes) per frame, encoded on the device (kbe_mjpeg_encode): the streams
         come to the host, not the pixels.  ``bgr``: the frames hold B, G, R (what Pipeline renders from a cv2.imread image).  One
         synchronisation for the offsets and the status word, then exactly offsets[n] bytes are copied.  ``cap``: the stream buffer's
         size (default: a quarter of the raw frames -- photographs at quality 92 take about a tenth); when the streams do not fit,
         the call is repeated once with a buffer of the true size, which the first run has reported."""
-        if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.size(3) == 3 and frames.size(0) >= 1):
-            raise KbeError('mjpeg_encode takes a uint8 [n,H,W,3] tensor on the GPU')
-        n, H, W, _ = frames.shape
-        base, step = _ptr(frames, torch.uint8).value, H * W * 3
-        pointers = (ctypes.c_void_p * n)(*[base + i * step for i in range(n)])
-        device = frames.device
-        scratch = torch.empty((int(self.lib.kbe_mjpeg_scratch_bytes(_i(W), _i(H), _i(n))) + 7) // 8, dtype=torch.int64, device=device)
-        meta = torch.empty(n + 2, dtype=torch.int64, device=device)          # offsets [n + 1], then the status word
-        status = ctypes.c_void_p(meta.data_ptr() + 8 * (n + 1))
-        cap = int(cap) if cap is not None else n * (1024 + step // 4)
-        for attempt in (0, 1):
-            streams = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
-            self._check(self.lib.kbe_mjpeg_encode(pointers, _i(n), _i(W), _i(H), _i(3 * W), _i(int(quality)), _i(KBE_MJPEG_BGR if bgr else 0), _ptr(scratch, torch.int64),
-                                                  _ptr(streams, torch.uint8), _z(cap), _ptr(meta, torch.int64), status, _stream()), 'kbe_mjpeg_encode')
-            host = meta.cpu()                                               # (the one synchronisation)
-            offsets, overflow = host[:n + 1].tolist(), int(host[n + 1].item()) & 0xFFFFFFFF
-            if not overflow:
-                break
-            if attempt == 1:
-                raise KbeError('kbe_mjpeg_encode: %d bytes do not fit a buffer of %d' % (offsets[n], cap))
-            cap = offsets[n]
-        data = streams[:offsets[n]].cpu().numpy()
-        return [data[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
+        return self._encode('mjpeg', frames, (int(quality), KBE_MJPEG_BGR if bgr else 0), cap, lambda n, step: n * (1024 + step // 4))
 
-    # -- PNG frames on the device ----------------------------------------------------------
     def png_encode(self, frames, bgr=False, cap=None):
         """uint8 [n,H,W,3] frames in HBM -> one PNG file (bytes) per frame, encoded on the device (kbe_png_encode): lossless, a file decodes
         to its frame.  ``bgr``: the frames hold B, G, R (what Pipeline renders from a cv2.imread image); the files hold R, G, B either way.
         One synchronisation for the offsets and the status word, then exactly offsets[n] bytes are copied.  ``cap``: the files' buffer
         (default: the raw size of the frames plus a kilobyte per frame -- only noise needs more); when the files do not fit, the call is
         repeated once with a buffer of the true size, which the first run has reported."""
-        if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.size(3) == 3 and frames.size(0) >= 1):
-            raise KbeError('png_encode takes a uint8 [n,H,W,3] tensor on the GPU')
-        n, H, W, _ = frames.shape
-        base, step = _ptr(frames, torch.uint8).value, H * W * 3
-        pointers = (ctypes.c_void_p * n)(*[base + i * step for i in range(n)])
-        device = frames.device
-        scratch = torch.empty((int(self.lib.kbe_png_scratch_bytes(_i(W), _i(H), _i(n))) + 7) // 8 + 1, dtype=torch.int64, device=device)
-        meta = torch.empty(n + 2, dtype=torch.int64, device=device)          # offsets [n + 1], then the status word
-        status = ctypes.c_void_p(meta.data_ptr() + 8 * (n + 1))
-        cap = int(cap) if cap is not None else n * (1024 + step)
-        for attempt in (0, 1):
-            files = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
-            self._check(self.lib.kbe_png_encode(pointers, _i(n), _i(W), _i(H), _i(3 * W), _i(KBE_PNG_BGR if bgr else 0), _ptr(scratch, torch.int64),
-                                                _ptr(files, torch.uint8), _z(cap), _ptr(meta, torch.int64), status, _stream()), 'kbe_png_encode')
-            host = meta.cpu()                                               # (the one synchronisation)
-            offsets, overflow = host[:n + 1].tolist(), int(host[n + 1].item()) & 0xFFFFFFFF
-            if not overflow:
-                break
-            if attempt == 1:
-                raise KbeError('kbe_png_encode: %d bytes do not fit a buffer of %d' % (offsets[n], cap))
-            cap = offsets[n]
-        data = files[:offsets[n]].cpu().numpy()
-        return [data[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
+        return self._encode('png', frames, (KBE_PNG_BGR if bgr else 0,), cap, lambda n, step: n * (1024 + step))
 
     # -- torch glue ---------------------------------------------------------------------
     def depth_to_points(self, depth, focal, valid=None):

@@ -20,7 +20,6 @@ using namespace kbe_mjpeg;
 
 namespace {
 
-constexpr int kFramesPerLaunch = 12;
 constexpr int kGroupIntervals = 4;                                              // intervals per workgroup: one per wave in the entropy phase
 constexpr int kGroupBlocks = kGroupIntervals * kRestartMcus * 6;                // 96 blocks
 constexpr int kEncodeThreads = 64 * kGroupIntervals;
@@ -157,20 +156,6 @@ __global__ __launch_bounds__(kEncodeThreads) void k_mjpeg_encode(const EncodeArg
     }
 }
 
-struct ScratchLayout { size_t counts, starts, sums, bytes; };       // byte offsets
-
-ScratchLayout scratch_layout(int W, int H, int n_frames)
-{
-    const Geometry g = geometry(W, H, 0, 0);
-    const size_t n = (size_t) (n_frames < kFramesPerLaunch ? n_frames : kFramesPerLaunch) * (size_t) g.intervals;
-    ScratchLayout s;
-    s.counts = 0;
-    s.starts = (n * 4 + 7) & ~(size_t) 7;
-    s.sums = s.starts + n * 8;
-    s.bytes = s.sums + ((n + kScanThreads - 1) / kScanThreads) * 8;
-    return s;
-}
-
 }  // namespace
 
 extern "C" {
@@ -182,40 +167,26 @@ size_t kbe_mjpeg_bound(int W, int H)
 
 size_t kbe_mjpeg_scratch_bytes(int W, int H, int n_frames)
 {
-    return W > 0 && H > 0 && W <= 65535 && H <= 65535 && n_frames > 0 ? scratch_layout(W, H, n_frames).bytes : 0;
+    return W > 0 && H > 0 && W <= 65535 && H <= 65535 && n_frames > 0 ? units_layout((size_t) geometry(W, H, 0, 0).intervals, n_frames, 0).bytes : 0;
 }
 
 int kbe_mjpeg_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H, int stride_bytes, int quality, int flags, void* scratch, uint8_t* streams, size_t cap,
                      uint64_t* offsets, int* status, kbe_stream_t stream)
 {
-    KBE_REQUIRE(frames_u8 && n_frames >= 1 && W > 0 && H > 0 && W <= 65535 && H <= 65535, "kbe_mjpeg_encode: bad frames or size");
-    KBE_REQUIRE(stride_bytes >= 3 * W && quality >= 1 && quality <= 100 && (flags & ~KBE_MJPEG_BGR) == 0, "kbe_mjpeg_encode: bad stride, quality or flags");
-    KBE_REQUIRE(scratch && ((uintptr_t) scratch & 7) == 0 && offsets && ((uintptr_t) offsets & 7) == 0 && status && (streams || cap == 0), "kbe_mjpeg_encode: bad buffers");
-    for (int i = 0; i < n_frames; i++) KBE_REQUIRE(frames_u8[i], "kbe_mjpeg_encode: null frame");
+    const UnitsCall c = { "kbe_mjpeg_encode", frames_u8, n_frames, W, H, scratch, streams, cap, offsets, status, (hipStream_t) stream };
+    const int rc = units_check(c, [&]() -> const char* {
+        return stride_bytes >= 3 * W && quality >= 1 && quality <= 100 && (flags & ~KBE_MJPEG_BGR) == 0 ? nullptr : "bad stride, quality or flags";
+    });
+    if (rc != KBE_OK) return rc;
 
     EncodeArgs a;
     a.g = geometry(W, H, stride_bytes, flags);
     host::tables_build(W, H, quality, &a.t, kRestartMcus);
-    const ScratchLayout lay = scratch_layout(W, H, n_frames);
-    uint32_t* counts = (uint32_t*) ((char*) scratch + lay.counts);
-    uint64_t* starts = (uint64_t*) ((char*) scratch + lay.starts);
-    uint64_t* sums = (uint64_t*) ((char*) scratch + lay.sums);
-    hipStream_t s = (hipStream_t) stream;
-    const unsigned groups = (unsigned) ((a.g.intervals + kGroupIntervals - 1) / kGroupIntervals);
-
-    for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) a.frames[i] = i < nf ? frames_u8[f0 + i] : nullptr;
-        const size_t n = (size_t) nf * (size_t) a.g.intervals, n_sums = (n + kScanThreads - 1) / kScanThreads;
-        hipLaunchKernelGGL(k_mjpeg_encode<false>, dim3(groups, (unsigned) nf), dim3(kEncodeThreads), 0, s, a, counts, (const uint64_t*) starts, streams, (uint64_t) cap);
-        hipLaunchKernelGGL(k_units_sums, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, sums);
-        hipLaunchKernelGGL(k_units_scan_sums, dim3(1), dim3(kSumsThreads), 0, s, sums, n_sums, offsets, f0, nf, (uint64_t) cap, status);
-        hipLaunchKernelGGL(k_units_starts, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, (const uint64_t*) sums, a.g.intervals, starts, offsets, f0);
-        hipLaunchKernelGGL(k_mjpeg_encode<true>, dim3(groups, (unsigned) nf), dim3(kEncodeThreads), 0, s, a, counts, (const uint64_t*) starts, streams, (uint64_t) cap);
-        const int rc = launched("kbe_mjpeg_encode");
-        if (rc != KBE_OK) return rc;
-    }
-    return KBE_OK;
+    return units_encode(c, a, a.g.intervals, 0, [&](bool store, int, int nf, uint32_t* counts, const uint64_t* starts, uint32_t*) {
+        const dim3 grid((unsigned) ((a.g.intervals + kGroupIntervals - 1) / kGroupIntervals), (unsigned) nf);
+        if (!store) hipLaunchKernelGGL(k_mjpeg_encode<false>, grid, dim3(kEncodeThreads), 0, c.s, a, counts, starts, streams, (uint64_t) cap);
+        else hipLaunchKernelGGL(k_mjpeg_encode<true>, grid, dim3(kEncodeThreads), 0, c.s, a, counts, starts, streams, (uint64_t) cap);
+    });
 }
 
 }  // extern "C"

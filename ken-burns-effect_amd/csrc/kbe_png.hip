@@ -24,7 +24,6 @@ using namespace kbe_png;
 
 namespace {
 
-constexpr int kFramesPerLaunch = 12;
 constexpr int kEncodeThreads = 256;
 constexpr int kPieceBytes = kSegmentBytes / kEncodeThreads;                     // a lane's piece of a segment
 constexpr int kOutWords = (kSegmentBytes + 5 + 3) / 4 + 1;                      // a segment's bytes are at most its stored form's
@@ -256,21 +255,6 @@ __global__ __launch_bounds__(kEncodeThreads) void k_png_tail(const EncodeArgs a,
     if (tid < kTailBytes && at + size - kTailBytes + tid < cap) files[at + size - kTailBytes + tid] = s_tail[tid];
 }
 
-struct ScratchLayout { size_t counts, starts, sums, marks, bytes; };       // byte offsets
-
-ScratchLayout scratch_layout(int W, int H, int n_frames)
-{
-    const Geometry g = geometry(W, H, 0, 0);
-    const size_t n = (size_t) (n_frames < kFramesPerLaunch ? n_frames : kFramesPerLaunch) * (size_t) g.segments;
-    ScratchLayout s;
-    s.counts = 0;
-    s.starts = (n * 4 + 7) & ~(size_t) 7;
-    s.sums = s.starts + n * 8;
-    s.marks = s.sums + ((n + kScanThreads - 1) / kScanThreads) * 8;
-    s.bytes = s.marks + n * kMarkWords * 4;
-    return s;
-}
-
 }  // namespace
 
 extern "C" {
@@ -282,17 +266,18 @@ size_t kbe_png_bound(int W, int H)
 
 size_t kbe_png_scratch_bytes(int W, int H, int n_frames)
 {
-    return file_bound(W, H) && n_frames > 0 ? scratch_layout(W, H, n_frames).bytes : 0;
+    return file_bound(W, H) && n_frames > 0 ? units_layout(geometry(W, H, 0, 0).segments, n_frames, kMarkWords).bytes : 0;
 }
 
 int kbe_png_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H, int stride_bytes, int flags, void* scratch, uint8_t* files, size_t cap, uint64_t* offsets,
                    int* status, kbe_stream_t stream)
 {
-    KBE_REQUIRE(frames_u8 && n_frames >= 1 && W > 0 && H > 0 && W <= 65535 && H <= 65535, "kbe_png_encode: bad frames or size");
-    KBE_REQUIRE(file_bound(W, H) != 0, "kbe_png_encode: a frame's file would not stay below 2^31 bytes");
-    KBE_REQUIRE(stride_bytes >= 3 * W && (flags & ~KBE_PNG_BGR) == 0, "kbe_png_encode: bad stride or flags");
-    KBE_REQUIRE(scratch && ((uintptr_t) scratch & 7) == 0 && offsets && ((uintptr_t) offsets & 7) == 0 && status && (files || cap == 0), "kbe_png_encode: bad buffers");
-    for (int i = 0; i < n_frames; i++) KBE_REQUIRE(frames_u8[i], "kbe_png_encode: null frame");
+    const UnitsCall c = { "kbe_png_encode", frames_u8, n_frames, W, H, scratch, files, cap, offsets, status, (hipStream_t) stream };
+    const int rc = units_check(c, [&]() -> const char* {
+        if (file_bound(W, H) == 0) return "a frame's file would not stay below 2^31 bytes";
+        return stride_bytes >= 3 * W && (flags & ~KBE_PNG_BGR) == 0 ? nullptr : "bad stride or flags";
+    });
+    if (rc != KBE_OK) return rc;
 
     EncodeArgs a;
     a.g = geometry(W, H, stride_bytes, flags);
@@ -302,28 +287,12 @@ int kbe_png_encode(const uint8_t* const* frames_u8, int n_frames, int W, int H, 
         a.pw = t.pw;
         for (int i = 0; i <= kLeadBytes; i++) a.lead[i] = t.lead[i];
     }
-    const ScratchLayout lay = scratch_layout(W, H, n_frames);
-    uint32_t* counts = (uint32_t*) ((char*) scratch + lay.counts);
-    uint64_t* starts = (uint64_t*) ((char*) scratch + lay.starts);
-    uint64_t* sums = (uint64_t*) ((char*) scratch + lay.sums);
-    uint32_t* marks = (uint32_t*) ((char*) scratch + lay.marks);
-    hipStream_t s = (hipStream_t) stream;
-
-    for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) a.frames[i] = i < nf ? frames_u8[f0 + i] : nullptr;
-        const size_t n = (size_t) nf * (size_t) a.g.segments, n_sums = (n + kScanThreads - 1) / kScanThreads;
+    return units_encode(c, a, (int) a.g.segments, kMarkWords, [&](bool store, int f0, int nf, uint32_t* counts, const uint64_t* starts, uint32_t* marks) {
         const dim3 grid(a.g.segments, (unsigned) nf);
-        hipLaunchKernelGGL(k_png_encode<false>, grid, dim3(kEncodeThreads), 0, s, a, counts, (const uint64_t*) starts, (const uint64_t*) offsets, f0, marks, files, (uint64_t) cap);
-        hipLaunchKernelGGL(k_units_sums, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, sums);
-        hipLaunchKernelGGL(k_units_scan_sums, dim3(1), dim3(kSumsThreads), 0, s, sums, n_sums, offsets, f0, nf, (uint64_t) cap, status);
-        hipLaunchKernelGGL(k_units_starts, dim3((unsigned) n_sums), dim3(kScanThreads), 0, s, (const uint32_t*) counts, n, (const uint64_t*) sums, (int) a.g.segments, starts, offsets, f0);
-        hipLaunchKernelGGL(k_png_encode<true>, grid, dim3(kEncodeThreads), 0, s, a, counts, (const uint64_t*) starts, (const uint64_t*) offsets, f0, marks, files, (uint64_t) cap);
-        hipLaunchKernelGGL(k_png_tail, dim3((unsigned) nf), dim3(kEncodeThreads), 0, s, a, (const uint32_t*) marks, (const uint64_t*) offsets, f0, files, (uint64_t) cap);
-        const int rc = launched("kbe_png_encode");
-        if (rc != KBE_OK) return rc;
-    }
-    return KBE_OK;
+        if (!store) hipLaunchKernelGGL(k_png_encode<false>, grid, dim3(kEncodeThreads), 0, c.s, a, counts, starts, (const uint64_t*) offsets, f0, marks, files, (uint64_t) cap);
+        else hipLaunchKernelGGL(k_png_encode<true>, grid, dim3(kEncodeThreads), 0, c.s, a, counts, starts, (const uint64_t*) offsets, f0, marks, files, (uint64_t) cap);
+        if (store) hipLaunchKernelGGL(k_png_tail, dim3((unsigned) nf), dim3(kEncodeThreads), 0, c.s, a, (const uint32_t*) marks, (const uint64_t*) offsets, f0, files, (uint64_t) cap);
+    });
 }
 
 }  // extern "C"

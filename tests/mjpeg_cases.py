@@ -1,4 +1,4 @@
-"""What tests/test_mjpeg_stream.py (CPU) and tests/test_mjpeg_gpu.py share: the CPU twin of the device-side Motion-JPEG encoder
+"""What tests/test_mjpeg_stream.py (CPU) and the GPU suites (tests/test_encoders_gpu.py, tests/test_mjpeg_gpu.py) share: the CPU twin of the device-side Motion-JPEG encoder
 (tests/mjpeg_check.cpp: csrc/kbe_mjpeg_block.h compiled by g++), the frames of the cases, and a reader of a stream's markers."""
 import functools
 import os

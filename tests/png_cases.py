@@ -1,4 +1,4 @@
-"""What tests/test_png_stream.py (CPU) and tests/test_png_gpu.py share: the CPU twin of the device-side PNG encoder (tests/png_check.cpp:
+"""What tests/test_png_stream.py (CPU) and the GPU suites (tests/test_encoders_gpu.py, tests/test_png_gpu.py) share: the CPU twin of the device-side PNG encoder (tests/png_check.cpp:
 csrc/kbe_png_block.h compiled by g++), the frames of the cases, and a reader of a PNG's chunks."""
 import functools
 import os

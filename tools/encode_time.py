@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Frames that lie in HBM -> Motion-JPEG streams in host memory, two ways in the SAME run, taking turns:
-  device: HipKernels.mjpeg_encode (kbe_mjpeg_encode: the GPU encodes, the streams cross the link);
-  host:   the frames cross the link raw into pinned memory and libkbe_jpeg.so encodes them on host threads (kbe_jpeg_encode_batch).
+"""Frames that lie in HBM -> Motion-JPEG streams (--format mjpeg) or the PNG files of --write-frames (--format png) in host memory, two ways
+in the SAME run, taking turns:
+  device: HipKernels.mjpeg_encode / png_encode (kbe_mjpeg_encode, kbe_png_encode: the GPU encodes, the streams or files cross the link);
+  host:   the frames cross the link raw into pinned memory and the writers' host threads encode them (mjpeg: libkbe_jpeg.so,
+          kbe_jpeg_encode_batch; png: pipeline.png_bytes, zlib level 1).
 Wall clock around calls that end with the bytes on the host (the device's ends in a device synchronise), every arm warmed up, SECONDS per
 arm and size.  One JSON line per size on stdout and, with --out, in a file.  --profile: nothing but ROUNDS device encodes of each size
 (for a `rocprofv3 --kernel-trace --stats` run of its own).  Needs a GPU."""
@@ -35,18 +37,20 @@ def photo_like(n, size, device):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--format', required=True, choices=['mjpeg', 'png'])
     ap.add_argument('--sizes', default='512x64,1024x75', help='SIZExFRAMES, comma separated')
     ap.add_argument('--seconds', type=float, default=3.0)
-    ap.add_argument('--quality', type=int, default=92)
+    ap.add_argument('--quality', type=int, default=92, help='mjpeg')
     ap.add_argument('--threads', type=int, default=16, help='host threads of the host arm')
     ap.add_argument('--out', default=None)
     ap.add_argument('--profile', action='store_true')
     ap.add_argument('--rounds', type=int, default=5)
     args = ap.parse_args()
-    assert torch.cuda.is_available(), 'mjpeg_time.py measures on a GPU'
+    assert torch.cuda.is_available(), 'encode_time.py measures on a GPU'
     K = _native.kernels()
-    kind, jpeg_lib = pipeline.jpeg_encoder()
-    assert kind == 'native'
+    mjpeg = args.format == 'mjpeg'
+    assert not mjpeg or pipeline.jpeg_encoder()[0] == 'native'
+    own = (args.quality, 0) if mjpeg else (0,)                      # the entry's integers between the stride and the scratch
     pipeline.WRITER_THREADS = args.threads
     os.environ.pop('KBE_WRITER_THREADS', None)
     lines = []
@@ -56,20 +60,21 @@ def main():
         pinned = torch.empty(frames.shape, dtype=torch.uint8).pin_memory()
 
         def device_arm():
-            return K.mjpeg_encode(frames, args.quality)
+            return K.mjpeg_encode(frames, args.quality) if mjpeg else K.png_encode(frames)
 
         def host_arm():
             pinned.copy_(frames, non_blocking=True)
             torch.cuda.current_stream().synchronize()
             host = pinned.numpy()
-            return pipeline._jpegs([host[i] for i in range(n)], args.quality)
+            rows = [host[i] for i in range(n)]
+            return pipeline._jpegs(rows, args.quality) if mjpeg else pipeline._on_threads(rows, pipeline.png_bytes)
 
         if args.profile:
             for _ in range(args.rounds):
                 device_arm()
             torch.cuda.synchronize()
             continue
-        on_device, on_host = device_arm(), host_arm()                   # warm-up, and the streams to look at
+        on_device, on_host = device_arm(), host_arm()                   # warm-up, and the bytes to look at
         device_arm(), host_arm()
         times = {'device': [], 'host': []}
         while min(sum(times['device']), sum(times['host'])) < args.seconds:
@@ -79,36 +84,37 @@ def main():
                 arm()
                 torch.cuda.synchronize()
                 times[name].append(time.perf_counter() - t0)
-        # the device alone: the five launches of a call on buffers that exist, HIP events
-        lib = K.lib
-        scratch = torch.empty(int(lib.kbe_mjpeg_scratch_bytes(size, size, n)) // 8 + 1, dtype=torch.int64, device='cuda')
+        # the device alone: the launches of a call on buffers that exist, HIP events
+        scratch = torch.empty(int(getattr(K.lib, 'kbe_%s_scratch_bytes' % args.format)(size, size, n)) // 8 + 1, dtype=torch.int64, device='cuda')
         cap = sum(len(s) for s in on_device)
-        streams = torch.empty(cap, dtype=torch.uint8, device='cuda')
+        out = torch.empty(cap, dtype=torch.uint8, device='cuda')
         meta = torch.empty(n + 2, dtype=torch.int64, device='cuda')
         pointers = (ctypes.c_void_p * n)(*[frames.data_ptr() + i * size * size * 3 for i in range(n)])
         kernel_ms = []
         for _ in range(7):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            rc = lib.kbe_mjpeg_encode(pointers, n, size, size, 3 * size, args.quality, 0, ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(streams.data_ptr()), ctypes.c_size_t(cap),
-                                      ctypes.c_void_p(meta.data_ptr()), ctypes.c_void_p(meta.data_ptr() + 8 * (n + 1)), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            rc = K.encode_raw(args.format, pointers, n, size, size, 3 * size, own, scratch.data_ptr(), out.data_ptr(), cap, meta.data_ptr(), meta.data_ptr() + 8 * (n + 1))
             e1.record()
             torch.cuda.synchronize()
             assert rc == 0
             kernel_ms.append(e0.elapsed_time(e1))
-        # what the restart intervals cost in bytes, and that the picture is there
         from PIL import Image
-        first = frames[0].cpu().numpy()
-        decoded = np.asarray(Image.open(io.BytesIO(on_device[0])).convert('RGB')).astype(np.float64)
-        psnr = 10.0 * np.log10(255.0 ** 2 / max(np.mean((decoded - first) ** 2), 1e-12))
-        line = {'what': 'frames in HBM -> Motion-JPEG streams on the host', 'size': size, 'frames': n, 'quality': args.quality, 'host_threads': args.threads,
-                'device_ms_per_video': {'median': 1e3 * float(np.median(times['device'])), 'min': 1e3 * min(times['device']), 'max': 1e3 * max(times['device']), 'calls': len(times['device'])},
-                'host_ms_per_video': {'median': 1e3 * float(np.median(times['host'])), 'min': 1e3 * min(times['host']), 'max': 1e3 * max(times['host']), 'calls': len(times['host'])},
-                'device_over_host_speedup': float(np.median(times['host']) / np.median(times['device'])),
-                'device_kernels_only_ms_per_video': {'median': float(np.median(kernel_ms)), 'min': min(kernel_ms)},
-                'device_stream_bytes': cap, 'host_stream_bytes': sum(len(s) for s in on_host), 'raw_bytes': n * size * size * 3,
-                'restart_interval_overhead': cap / sum(len(s) for s in on_host) - 1.0, 'first_frame_psnr_db': float(psnr),
-                'gpu': torch.cuda.get_device_name(0)}
+        times_of = {name + '_ms_per_video': {'median': 1e3 * float(np.median(t)), 'min': 1e3 * min(t), 'max': 1e3 * max(t), 'calls': len(t)} for name, t in times.items()}
+        line = dict(times_of, size=size, frames=n, host_threads=args.threads, device_over_host_speedup=float(np.median(times['host']) / np.median(times['device'])),
+                    device_kernels_only_ms_per_video={'median': float(np.median(kernel_ms)), 'min': min(kernel_ms)}, raw_bytes=n * size * size * 3,
+                    gpu=torch.cuda.get_device_name(0))
+        host_bytes = sum(len(s) for s in on_host)
+        if mjpeg:       # what the restart intervals cost in bytes, and that the picture is there
+            first = frames[0].cpu().numpy()
+            decoded = np.asarray(Image.open(io.BytesIO(on_device[0])).convert('RGB')).astype(np.float64)
+            psnr = 10.0 * np.log10(255.0 ** 2 / max(np.mean((decoded - first) ** 2), 1e-12))
+            line.update(what='frames in HBM -> Motion-JPEG streams on the host', quality=args.quality, device_stream_bytes=cap, host_stream_bytes=host_bytes,
+                        restart_interval_overhead=cap / host_bytes - 1.0, first_frame_psnr_db=float(psnr))
+        else:           # lossless: the first and the last file decode to their frames
+            for i in (0, n - 1):
+                assert np.array_equal(np.asarray(Image.open(io.BytesIO(on_device[i])).convert('RGB')), frames[i].cpu().numpy())
+            line.update(what='frames in HBM -> PNG files on the host', device_file_bytes=cap, host_file_bytes=host_bytes, device_over_host_bytes=cap / host_bytes)
         print(json.dumps(line), flush=True)
         lines.append(line)
     if args.out and lines:
