@@ -7,13 +7,16 @@ refuses tensors that are not contiguous fp32 CUDA(=HIP) tensors.
 The wrappers take torch tensors only to obtain ``data_ptr()`` and the current HIP
 stream -- the same contract the reference had with CuPy
 (``/root/reference/utils/common.py:516-521``), minus the per-shape JIT.
+
+The types of every entry come from the header (:func:`prototypes`, ``_cabi``): :func:`load` sets them, the wrappers pass plain
+Python values through :meth:`HipKernels._call`, and a call that does not fit the header is refused before it is made.
 """
 import ctypes
 import os
 
 import torch
 
-from . import video_shape
+from . import _cabi, video_shape
 # (the flag bits under the header's names, and the rules and thresholds of a video call's shape that lived here before video_shape.py did)
 from .video_shape import (DEFAULT_FILL_GROUP, DEFAULT_HOST_LANES, FUSED_DENSE, FUSED_HOST_GROUP, KBE_STAGE_FUSED_LEAN, KBE_STAGE_FUSED_ROOMY,  # noqa: F401
                           KBE_STAGE_PROJECT, KBE_VIDEO_FILL_DIST, KBE_VIDEO_FILL_GROUP, KBE_VIDEO_GROUP, KBE_VIDEO_FREE_TRANSFERS,
@@ -22,16 +25,7 @@ from .video_shape import (DEFAULT_FILL_GROUP, DEFAULT_HOST_LANES, FUSED_DENSE, F
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('KBE_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libkbe_hip.so')      # (KBE_LIB_PATH: a variant build of the same ABI -- measurements)
-
-# every symbol include/kbe.h declares (tests check the library exports exactly these)
-SYMBOLS = (
-    'kbe_abi_version', 'kbe_last_error', 'kbe_device_info', 'kbe_selftest_err', 'kbe_selftest_division', 'kbe_zkeys_clear', 'kbe_zsplat', 'kbe_zkeys_decode',
-    'kbe_degrid', 'kbe_degrid_serial', 'kbe_accumulate', 'kbe_normalize', 'kbe_render_pointcloud', 'kbe_fill_disocclusion',
-    'kbe_frame_scratch_bytes', 'kbe_frame_scratch_init', 'kbe_render_frame', 'kbe_render_frame_stages', 'kbe_render_frame_group', 'kbe_cloud_pack_bytes', 'kbe_cloud_pack', 'kbe_render_frame_fused', 'kbe_render_frame_group_fused', 'kbe_render_frame_group_ahead_ok', 'kbe_render_frame_group_ahead', 'kbe_video_scratch_stride', 'kbe_video_stage_bytes', 'kbe_render_video', 'kbe_render_pointcloud_tiled', 'kbe_generate_mask', 'kbe_frame_u8', 'kbe_crop_resize_u8', 'kbe_depth_to_points', 'kbe_shift_points',
-    'kbe_spatial_filter', 'kbe_laplacian_valid', 'kbe_pconv_epilogue', 'kbe_prelu_mask', 'kbe_bias_act', 'kbe_upsample2x_act', 'kbe_frame_scratch_init_sets', 'kbe_video_handoff_status',
-    'kbe_mjpeg_bound', 'kbe_mjpeg_scratch_bytes', 'kbe_mjpeg_encode',
-    'kbe_png_bound', 'kbe_png_scratch_bytes', 'kbe_png_encode',
-)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'kbe.h')     # the contract: every entry's types are read from it (prototypes)
 
 ABI_VERSION = 13
 MAX_LANES = 8          # KBE_MAX_LANES
@@ -90,41 +84,48 @@ def host_lanes(lanes, n_points, W, H, frame_bytes):
 
 
 _lib = None
+_protos = None
 
 
 class KbeError(RuntimeError):
     pass
 
 
+def prototypes():
+    """{entry: (restype, [argtypes])} of every entry include/kbe.h declares, in its order (_cabi.prototypes), read once."""
+    global _protos
+    if _protos is None:
+        if not os.path.exists(HEADER_PATH):
+            raise KbeError('%s is missing: the binding takes the types of every entry of libkbe_hip.so from it' % HEADER_PATH)
+        with open(HEADER_PATH) as f:
+            _protos = _cabi.prototypes(f.read(), 'KBE_API')
+    return _protos
+
+
+def __getattr__(name):
+    if name == 'SYMBOLS':          # every symbol include/kbe.h declares (tests check the library exports exactly these)
+        return tuple(prototypes())
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
+
+
 def load():
-    """Loads the HIP library once; fails loudly when it has not been built."""
+    """Loads the HIP library once and types every entry from the header; fails loudly when it has not been built."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
         raise KbeError('HIP extension not built: %s is missing. Run `python -c "import __graft_entry__ as g; g.build()"` '
                        '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
+    protos = prototypes()
     lib = ctypes.CDLL(LIB_PATH)
-    for name in SYMBOLS:
+    for name in protos:
         if not hasattr(lib, name):
             raise KbeError('libkbe_hip.so does not export %s (stale build?)' % name)
-        getattr(lib, name).restype = ctypes.c_int
-    lib.kbe_last_error.restype = ctypes.c_char_p
-    lib.kbe_frame_scratch_bytes.restype = ctypes.c_size_t
-    lib.kbe_video_scratch_stride.restype = ctypes.c_size_t
-    lib.kbe_video_stage_bytes.restype = ctypes.c_size_t
-    lib.kbe_cloud_pack_bytes.restype = ctypes.c_size_t
-    lib.kbe_mjpeg_bound.restype = ctypes.c_size_t
-    lib.kbe_mjpeg_scratch_bytes.restype = ctypes.c_size_t
-    lib.kbe_png_bound.restype = ctypes.c_size_t
-    lib.kbe_png_scratch_bytes.restype = ctypes.c_size_t
+    _cabi.bind(lib, protos)
     if lib.kbe_abi_version() != ABI_VERSION:
         raise KbeError('libkbe_hip.so ABI %d != expected %d' % (lib.kbe_abi_version(), ABI_VERSION))
     _lib = lib
     return lib
-
-
-_i, _d, _f, _z = ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_size_t
 
 
 def _ptr(t, dtype=torch.float32):
@@ -238,17 +239,31 @@ class HipKernels:
         if rc != 0:
             raise KbeError('%s failed (%d): %s' % (what, rc, self.lib.kbe_last_error().decode()))
 
+    def _raw(self, name, *args):
+        """The entry `name` of include/kbe.h with plain Python values -> what it returns.  ctypes holds the values to the header's types
+        (load); a surplus argument, which cdecl lets through, is refused here.  The entry is looked up on self.lib at each call (a tool
+        may have put a shim there)."""
+        proto = prototypes().get(name)
+        if proto is None:
+            raise KbeError('%s is not an entry of include/kbe.h' % name)
+        if len(args) != len(proto[1]):
+            raise KbeError('%s takes %d arguments, got %d' % (name, len(proto[1]), len(args)))
+        return getattr(self.lib, name)(*args)
+
+    def _call(self, name, *args, what=None):
+        """An entry that returns a status: KbeError with the library's text (under the label `what`, default the entry's name) unless KBE_OK."""
+        self._check(self._raw(name, *args), what or name)
+
     def selftest_err(self, z, focal, baseline):
         z = _f32c(z).reshape(-1)
         fast, exact = torch.empty_like(z), torch.empty_like(z)
-        self._check(self.lib.kbe_selftest_err(_ptr(z), _z(z.numel()), _d(float(focal)), _d(float(baseline)), _ptr(fast), _ptr(exact),
-                                              _stream()), 'kbe_selftest_err')
+        self._call('kbe_selftest_err', _ptr(z), z.numel(), float(focal), float(baseline), _ptr(fast), _ptr(exact), _stream())
         return fast, exact
 
     def selftest_division(self, num, den):
         num, den = _f32c(num).reshape(-1), _f32c(den).reshape(-1)
         fast, ieee = torch.empty_like(num), torch.empty_like(num)
-        self._check(self.lib.kbe_selftest_division(_ptr(num), _ptr(den), _z(num.numel()), _ptr(fast), _ptr(ieee), _stream()), 'kbe_selftest_division')
+        self._call('kbe_selftest_division', _ptr(num), _ptr(den), num.numel(), _ptr(fast), _ptr(ieee), _stream())
         return fast, ieee
 
     # -- render_pointcloud and its stages ------------------------------------------------
@@ -256,25 +271,22 @@ class HipKernels:
         points = _f32c(points)
         B, _, N = points.shape
         zkeys = torch.empty(B, 1, H, W, dtype=torch.int32, device=points.device)
-        self._check(self.lib.kbe_zkeys_clear(_ptr(zkeys, torch.int32), _z(zkeys.numel()), _stream()), 'kbe_zkeys_clear')
+        self._call('kbe_zkeys_clear', _ptr(zkeys, torch.int32), zkeys.numel(), _stream())
         winner = torch.empty(B, N, dtype=torch.int32, device=points.device) if want_winner else None
-        self._check(self.lib.kbe_zsplat(_ptr(points), _i(B), _i(N), _i(W), _i(H), _d(float(focal)), _d(float(baseline)),
-                                        _shift(shift3), _ptr(zkeys, torch.int32), _ptr(winner, torch.int32), _stream()),
-                    'kbe_zsplat')
+        self._call('kbe_zsplat', _ptr(points), B, N, W, H, float(focal), float(baseline), _shift(shift3), _ptr(zkeys, torch.int32),
+                   _ptr(winner, torch.int32), _stream())
         return zkeys, winner
 
     def zkeys_decode(self, zkeys):
         zee = torch.empty(zkeys.shape, dtype=torch.float32, device=zkeys.device)
-        self._check(self.lib.kbe_zkeys_decode(_ptr(zkeys, torch.int32), _z(zkeys.numel()), _ptr(zee), _stream()),
-                    'kbe_zkeys_decode')
+        self._call('kbe_zkeys_decode', _ptr(zkeys, torch.int32), zkeys.numel(), _ptr(zee), _stream())
         return zee
 
     def degrid(self, zkeys=None, zee=None):
         src = zkeys if zkeys is not None else zee
         B, _, H, W = src.shape
         out = torch.empty(B, 1, H, W, dtype=torch.float32, device=src.device)
-        self._check(self.lib.kbe_degrid(_ptr(zkeys, torch.int32), _ptr(None if zee is None else _f32c(zee)), _i(B), _i(W),
-                                        _i(H), _ptr(out), _stream()), 'kbe_degrid')
+        self._call('kbe_degrid', _ptr(zkeys, torch.int32), _ptr(None if zee is None else _f32c(zee)), B, W, H, _ptr(out), _stream())
         return out
 
     def degrid_serial(self, zkeys=None, zee=None):
@@ -283,8 +295,7 @@ class HipKernels:
         src = zkeys if zkeys is not None else zee
         B, _, H, W = src.shape
         out = torch.empty(B, 1, H, W, dtype=torch.float32, device=src.device)
-        self._check(self.lib.kbe_degrid_serial(_ptr(zkeys, torch.int32), _ptr(None if zee is None else _f32c(zee)), _i(B), _i(W),
-                                               _i(H), _ptr(out), _stream()), 'kbe_degrid_serial')
+        self._call('kbe_degrid_serial', _ptr(zkeys, torch.int32), _ptr(None if zee is None else _f32c(zee)), B, W, H, _ptr(out), _stream())
         return out
 
     def accumulate(self, points, data, zee, focal, baseline, shift3=None):
@@ -292,17 +303,15 @@ class HipKernels:
         B, C, N = data.shape
         _, _, H, W = zee.shape
         acc = torch.zeros(B, C + 1, H, W, dtype=torch.float32, device=points.device)
-        self._check(self.lib.kbe_accumulate(_ptr(points), _ptr(data), _i(B), _i(N), _i(C), _ptr(_f32c(zee)), _i(W), _i(H),
-                                            _d(float(focal)), _d(float(baseline)), _shift(shift3), _ptr(acc), _stream()),
-                    'kbe_accumulate')
+        self._call('kbe_accumulate', _ptr(points), _ptr(data), B, N, C, _ptr(_f32c(zee)), W, H, float(focal), float(baseline), _shift(shift3),
+                   _ptr(acc), _stream())
         return acc
 
     def normalize(self, acc):
         B, C1, H, W = acc.shape
         render = torch.empty(B, C1 - 1, H, W, dtype=torch.float32, device=acc.device)
         existing = torch.empty(B, 1, H, W, dtype=torch.float32, device=acc.device)
-        self._check(self.lib.kbe_normalize(_ptr(_f32c(acc)), _i(B), _i(C1 - 1), _i(W), _i(H), _ptr(render), _ptr(existing),
-                                           _stream()), 'kbe_normalize')
+        self._call('kbe_normalize', _ptr(_f32c(acc)), B, C1 - 1, W, H, _ptr(render), _ptr(existing), _stream())
         return render, existing
 
     def render_pointcloud(self, points, data, W, H, focal, baseline, tiled=None):
@@ -321,26 +330,22 @@ class HipKernels:
             key = (dev, W, H)
             scratch = self._tiled_scratch.get(key)
             if scratch is None:
-                scratch = torch.empty(int(self.lib.kbe_frame_scratch_bytes(_i(W), _i(H), _i(0))), dtype=torch.uint8, device=dev)
-                self._check(self.lib.kbe_frame_scratch_init(_ptr(scratch, torch.uint8), _i(W), _i(H), _stream()), 'kbe_frame_scratch_init')
+                scratch = torch.empty(int(self.lib.kbe_frame_scratch_bytes(W, H, 0)), dtype=torch.uint8, device=dev)
+                self._call('kbe_frame_scratch_init', _ptr(scratch, torch.uint8), W, H, _stream())
                 self._tiled_scratch = {key: scratch}           # one size at a time (200 MB at 1024^2)
             render = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
             existing = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
             for b in range(B):
-                self._check(self.lib.kbe_render_pointcloud_tiled(_ptr(points[b]), _ptr(data[b]), _i(N), _i(C), _i(W), _i(H),
-                                                                 _d(float(focal)), _d(float(baseline)), None, _ptr(scratch, torch.uint8),
-                                                                 _ptr(render[b]), _ptr(existing[b]), _stream()),
-                            'kbe_render_pointcloud_tiled')
+                self._call('kbe_render_pointcloud_tiled', _ptr(points[b]), _ptr(data[b]), N, C, W, H, float(focal), float(baseline), None,
+                           _ptr(scratch, torch.uint8), _ptr(render[b]), _ptr(existing[b]), _stream())
             return render, existing
         zkeys = torch.empty(B * H * W, dtype=torch.int32, device=dev)
         zee = torch.empty(B * H * W, dtype=torch.float32, device=dev)
         acc = torch.empty(B * (C + 1) * H * W, dtype=torch.float32, device=dev)
         render = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
         existing = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
-        self._check(self.lib.kbe_render_pointcloud(_ptr(points), _ptr(data), _i(B), _i(N), _i(C), _i(W), _i(H),
-                                                   _d(float(focal)), _d(float(baseline)), _ptr(zkeys, torch.int32),
-                                                   _ptr(zee), _ptr(acc), _ptr(render), _ptr(existing), _stream()),
-                    'kbe_render_pointcloud')
+        self._call('kbe_render_pointcloud', _ptr(points), _ptr(data), B, N, C, W, H, float(focal), float(baseline), _ptr(zkeys, torch.int32),
+                   _ptr(zee), _ptr(acc), _ptr(render), _ptr(existing), _stream())
         return render, existing
 
     # -- fill ---------------------------------------------------------------------------
@@ -348,8 +353,7 @@ class HipKernels:
         x, depth = _f32c(x), _f32c(depth)
         B, C, H, W = x.shape
         out = torch.empty_like(x)
-        self._check(self.lib.kbe_fill_disocclusion(_ptr(x), _ptr(depth), _i(B), _i(C), _i(W), _i(H), _ptr(out), _stream()),
-                    'kbe_fill_disocclusion')
+        self._call('kbe_fill_disocclusion', _ptr(x), _ptr(depth), B, C, W, H, _ptr(out), _stream())
         return out
 
     # -- the frame loop on the resident cloud ---------------------------------------------
@@ -371,11 +375,10 @@ class HipKernels:
         # one scratch per lane of the frame loop (render_video renders consecutive frames on `lanes` streams);
         # render_frame uses lane 0's
         lanes = max(1, min(MAX_LANES, int(os.environ.get('KBE_LANES', DEFAULT_LANES))))
-        stride = int(self.lib.kbe_video_scratch_stride(_i(W), _i(H), _i(N)))
+        stride = int(self.lib.kbe_video_scratch_stride(W, H, N))
         state['lanes'] = lanes
         state['scratch'] = torch.empty(lanes * stride, dtype=torch.uint8, device=dev)
-        self._check(self.lib.kbe_frame_scratch_init_sets(ctypes.c_void_p(state['scratch'].data_ptr()), _z(stride), _i(lanes), _i(W), _i(H), _stream()),
-                    'kbe_frame_scratch_init_sets')
+        self._call('kbe_frame_scratch_init_sets', state['scratch'].data_ptr(), stride, lanes, W, H, _stream())
         # Two routes for the scatter of a frame, same results (tests/test_hip_parity.py::test_fused_scatter_equals_the_bucket_path):
         #   fused   k_place -> k_frame on the packed cloud (kbe_cloud_pack, once per cloud): every point projected once, its
         #           12-byte placement stored in place, a tile pulls the sub-blocks listed for it, z-tile in LDS; no per-point
@@ -419,10 +422,9 @@ class HipKernels:
         """kbe_cloud_pack, once per cloud (on first use of the fused route)."""
         if 'packed' not in state:
             N, W, H = state['N'], state['W'], state['H']
-            state['packed'] = torch.empty(int(self.lib.kbe_cloud_pack_bytes(_i(N))), dtype=torch.uint8, device=state['points'].device)
-            self._check(self.lib.kbe_cloud_pack(_ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), _i(N), _i(W), _i(H),
-                                                _d(state['cloud_focal']), _i(state['raster_w']), _i(state['raster_n']),
-                                                _ptr(state['packed'], torch.uint8), _stream()), 'kbe_cloud_pack')
+            state['packed'] = torch.empty(int(self.lib.kbe_cloud_pack_bytes(N)), dtype=torch.uint8, device=state['points'].device)
+            self._call('kbe_cloud_pack', _ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), N, W, H, state['cloud_focal'],
+                       state['raster_w'], state['raster_n'], _ptr(state['packed'], torch.uint8), _stream())
 
     def render_frame(self, state, shift3, focal, baseline, render_f32=None, existing_f32=None, zee_f32=None,
                      zee_pre_f32=None, out=None, stages=7, fill_rect=None, fused=None, parity=-1):
@@ -435,19 +437,15 @@ class HipKernels:
         rect = _rect(fill_rect)
         if state.get('fused') if fused is None else fused:
             self._pack(state)
-            self._check(self.lib.kbe_render_frame_fused(_ptr(state['packed'], torch.uint8), _i(state['N']), _d(state['cloud_focal']),
-                                                        _i(state['W']), _i(state['H']), _d(float(focal)), _d(float(baseline)),
-                                                        _shift(shift3), _ptr(state['scratch'], torch.uint8), _ptr(frame, torch.uint8),
-                                                        _ptr(render_f32), _ptr(existing_f32), _ptr(zee_f32), _ptr(zee_pre_f32),
-                                                        _i((int(stages) & ~KBE_STAGE_PROJECT) | fused_build_bits()), rect, _i(int(parity)), _stream()), 'kbe_render_frame_fused')
+            self._call('kbe_render_frame_fused', _ptr(state['packed'], torch.uint8), state['N'], state['cloud_focal'], state['W'], state['H'],
+                       float(focal), float(baseline), _shift(shift3), _ptr(state['scratch'], torch.uint8), _ptr(frame, torch.uint8), _ptr(render_f32),
+                       _ptr(existing_f32), _ptr(zee_f32), _ptr(zee_pre_f32), (int(stages) & ~KBE_STAGE_PROJECT) | fused_build_bits(), rect,
+                       int(parity), _stream())
             return frame
-        self._check(self.lib.kbe_render_frame_stages(_ptr(state['points']), _ptr(state['image']), _ptr(state['depth']),
-                                                     _i(state['N']), _i(state['W']), _i(state['H']), _d(float(focal)),
-                                                     _d(float(baseline)), _shift(shift3), _ptr(state['scratch'], torch.uint8),
-                                                     _ptr(frame, torch.uint8), _ptr(render_f32), _ptr(existing_f32),
-                                                     _ptr(zee_f32), _ptr(zee_pre_f32), _i(int(stages)), rect, _i(state['raster_w']),
-                                                     _i(state['raster_n']), _stream()),
-                    'kbe_render_frame')
+        self._call('kbe_render_frame_stages', _ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), state['N'], state['W'], state['H'],
+                   float(focal), float(baseline), _shift(shift3), _ptr(state['scratch'], torch.uint8), _ptr(frame, torch.uint8), _ptr(render_f32),
+                   _ptr(existing_f32), _ptr(zee_f32), _ptr(zee_pre_f32), int(stages), rect, state['raster_w'], state['raster_n'], _stream(),
+                   what='kbe_render_frame')
         return frame
 
     def group_scratch(self, state, sets):
@@ -456,8 +454,7 @@ class HipKernels:
         stride = self.scratch_stride(state)
         if 'scratch_groups' not in state or state['scratch_groups'].numel() < sets * stride:
             state['scratch_groups'] = torch.empty(sets * stride, dtype=torch.uint8, device=state['points'].device)
-            self._check(self.lib.kbe_frame_scratch_init_sets(ctypes.c_void_p(state['scratch_groups'].data_ptr()), _z(stride), _i(sets), _i(state['W']), _i(state['H']),
-                                                             _stream()), 'kbe_frame_scratch_init_sets')
+            self._call('kbe_frame_scratch_init_sets', state['scratch_groups'].data_ptr(), stride, sets, state['W'], state['H'], _stream())
         return state['scratch_groups'], stride
 
     def _group_sets(self, state, *counts):
@@ -472,9 +469,8 @@ class HipKernels:
         scratch, stride = self.group_scratch(state, max(n, 4))
         focals, shifts, sets, frames, rect = _group_args(cameras, scratch, stride, out, fill_rect)
         zf = None if zbuf_flags is None else (ctypes.c_int * n)(*[int(v) for v in zbuf_flags])
-        self._check(self.lib.kbe_render_frame_group(_ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), _i(state['N']), _i(state['W']),
-                                                    _i(state['H']), _d(float(baseline)), _i(n), focals, shifts, sets, frames, zf, _i(int(stages)), rect,
-                                                    _i(state['raster_w']), _i(state['raster_n']), _stream()), 'kbe_render_frame_group')
+        self._call('kbe_render_frame_group', _ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), state['N'], state['W'], state['H'],
+                   float(baseline), n, focals, shifts, sets, frames, zf, int(stages), rect, state['raster_w'], state['raster_n'], _stream())
         return out
 
     def render_frame_group_fused(self, state, cameras, baseline, out, stages=6, parities=None, fill_rect=None):
@@ -484,9 +480,8 @@ class HipKernels:
         scratch, stride = self._group_sets(state, n)
         focals, shifts, sets, frames, rect = _group_args(cameras, scratch, stride, out, fill_rect)
         par = None if parities is None else (ctypes.c_int * n)(*[int(v) for v in parities])
-        self._check(self.lib.kbe_render_frame_group_fused(_ptr(state['packed'], torch.uint8), _i(state['N']), _d(state['cloud_focal']), _i(state['W']),
-                                                          _i(state['H']), _d(float(baseline)), _i(n), focals, shifts, sets, frames, par, _i(int(stages) | fused_build_bits()), rect,
-                                                          _stream()), 'kbe_render_frame_group_fused')
+        self._call('kbe_render_frame_group_fused', _ptr(state['packed'], torch.uint8), state['N'], state['cloud_focal'], state['W'], state['H'],
+                   float(baseline), n, focals, shifts, sets, frames, par, int(stages) | fused_build_bits(), rect, _stream())
         return out
 
     def render_frame_group_ahead(self, state, cameras, baseline, out, turn, placed, next_cameras=None, stages=6, fill_rect=None, next_turn=None):
@@ -504,9 +499,9 @@ class HipKernels:
             next_turn = [(turn[k] if k < n else turn[0]) + 1 for k in range(m)]
         turns = (ctypes.c_int * n)(*turn)
         nturns = (ctypes.c_int * m)(*[int(t) for t in next_turn]) if m else None
-        self._check(self.lib.kbe_render_frame_group_ahead(_ptr(state['packed'], torch.uint8), _i(state['N']), _d(state['cloud_focal']), _i(state['W']),
-                                                          _i(state['H']), _d(float(baseline)), _i(n), focals, shifts, sets, frames, turns, _i(1 if placed else 0),
-                                                          _i(m), nf, ns, nsets, nturns, _i(int(stages) | fused_build_bits()), rect, _d(self.near_depth(state)), _stream()), 'kbe_render_frame_group_ahead')
+        self._call('kbe_render_frame_group_ahead', _ptr(state['packed'], torch.uint8), state['N'], state['cloud_focal'], state['W'], state['H'],
+                   float(baseline), n, focals, shifts, sets, frames, turns, 1 if placed else 0, m, nf, ns, nsets, nturns,
+                   int(stages) | fused_build_bits(), rect, self.near_depth(state), _stream())
         return out
 
     def prepared_group_ahead(self, state, cameras, baseline, out, next_cameras, stages=2):
@@ -520,10 +515,11 @@ class HipKernels:
         focals, shifts, sets, frames, _ = _group_args(cameras, scratch, stride, out)
         nf, ns, nsets = _group_args(next_cameras, scratch, stride)[:3]
         turns, nturns = (ctypes.c_int * n)(), (ctypes.c_int * m)()
-        fixed = (_ptr(state['packed'], torch.uint8), _i(state['N']), _d(state['cloud_focal']), _i(state['W']), _i(state['H']), _d(float(baseline)), _i(n),
+        fixed = (_ptr(state['packed'], torch.uint8), state['N'], state['cloud_focal'], state['W'], state['H'], float(baseline), n,
                  focals, shifts, sets, frames, turns)
-        tail = (nf, ns, nsets, nturns, _i(int(stages) | fused_build_bits()), None, _d(self.near_depth(state)))
-        fn, check, zero = self.lib.kbe_render_frame_group_ahead, self._check, _i(0)
+        tail = (nf, ns, nsets, nturns, int(stages) | fused_build_bits(), None, self.near_depth(state))
+        fn, check = self.lib.kbe_render_frame_group_ahead, self._check
+        assert len(fixed) + 2 + len(tail) + 1 == len(prototypes()['kbe_render_frame_group_ahead'][1])       # (launch passes: fixed, placed, n_next, tail, stream)
         keep = (scratch, out)          # (the arrays hold raw addresses)
 
         def launch(turn, placed, place_next=True):
@@ -531,14 +527,14 @@ class HipKernels:
                 turns[k] = turn
             for k in range(m):
                 nturns[k] = turn + 1
-            check(fn(*fixed, _i(1 if placed else 0), _i(m) if place_next else zero, *tail, _stream()), 'kbe_render_frame_group_ahead')
+            check(fn(*fixed, 1 if placed else 0, m if place_next else 0, *tail, _stream()), 'kbe_render_frame_group_ahead')
         launch.keep = keep
         return launch
 
     def scratch_stride(self, state):
         """Bytes between two scratch sets of the cloud's frame size (kbe_video_scratch_stride), asked once per cloud."""
         if 'scratch_stride' not in state:
-            state['scratch_stride'] = int(self.lib.kbe_video_scratch_stride(_i(state['W']), _i(state['H']), _i(state['N'])))
+            state['scratch_stride'] = int(self.lib.kbe_video_scratch_stride(state['W'], state['H'], state['N']))
         return state['scratch_stride']
 
     def scratch_set_budget(self, state, budget_mb=None):
@@ -651,7 +647,7 @@ class HipKernels:
         shape = video_shape.call_shape(state['N'], W, H, bool(state.get('fused')), n, self.zooms_out(state, cameras), to_host, batch, lanes, sw,
                                        held, lambda: self.scratch_set_budget(state, sw.scratch_budget_mb))
         batch, fused = shape.batch, shape.fused
-        need = int(self.lib.kbe_video_stage_bytes(_i(W), _i(H), _i(lanes), _i(batch)))
+        need = int(self.lib.kbe_video_stage_bytes(W, H, lanes, batch))
         if 'stage' not in state or state['stage'].numel() < need:
             state['stage'] = torch.empty(need, dtype=torch.uint8, device=dev)
         if 'copy_stream' not in state:
@@ -661,24 +657,22 @@ class HipKernels:
         focals = (ctypes.c_double * max(n, 1))(*[float(c[0]) for c in cameras])
         shifts = (ctypes.c_float * max(3 * n, 1))(*[float(v) for c in cameras for v in c[1]])
         cw, ch = (0, 0) if crop is None else (int(crop[0]), int(crop[1]))
-        copy_stream = ctypes.c_void_p(state['copy_stream'].cuda_stream) if overlap and to_host else _stream()
+        copy_stream = state['copy_stream'].cuda_stream if overlap and to_host else _stream()
         if fused:
             self._pack(state)
         # one frame per launch renders on the lanes' own sets, more on the group scratch (shape.group sets per lane, allocated on first use)
         state['video_sets'] = shape.sets
         scratch = self.group_scratch(state, shape.sets)[0] if shape.group > 1 else state['scratch']
-        self._check(self.lib.kbe_render_video(_ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), _i(state['N']),
-                                              _i(W), _i(H), _d(float(baseline)), _i(n), focals, shifts, _i(cw), _i(ch),
-                                              _ptr(scratch, torch.uint8), _ptr(state['stage'], torch.uint8), _i(batch),
-                                              ctypes.c_void_p(host_out.data_ptr()), _i(state['raster_w']), _i(state['raster_n']),
-                                              _ptr(state['packed'], torch.uint8) if fused else None, _d(state['cloud_focal']),
-                                              _i(shape.flags), _stream(), copy_stream, _i(lanes), lane_streams, _d(self.near_depth(state) if fused else 0.0)), 'kbe_render_video')
+        self._call('kbe_render_video', _ptr(state['points']), _ptr(state['image']), _ptr(state['depth']), state['N'], W, H, float(baseline), n,
+                   focals, shifts, cw, ch, _ptr(scratch, torch.uint8), _ptr(state['stage'], torch.uint8), batch, host_out.data_ptr(),
+                   state['raster_w'], state['raster_n'], _ptr(state['packed'], torch.uint8) if fused else None, state['cloud_focal'], shape.flags,
+                   _stream(), copy_stream, lanes, lane_streams, self.near_depth(state) if fused else 0.0)
         return host_out
 
     def handoff_status(self):
         """After synchronising a delivered video's stream: raises KbeError when an SDMA hand-off of this process gave up waiting for its
         engine (kbe_video_handoff_status: the frames of that video are not all in host memory)."""
-        self._check(self.lib.kbe_video_handoff_status(), 'kbe_video_handoff_status')
+        self._call('kbe_video_handoff_status')
 
     def generate_mask_raw(self, points, shift, W, H, focal, baseline, want_tables=False):
         """generate_mask's kernel (common.py:696-817) -> masks [B,1,N] (and zee [B,1,H,W], ids [B,H,W] int32)."""
@@ -691,9 +685,8 @@ class HipKernels:
         masks = torch.empty(B, 1, N, dtype=torch.float32, device=dev)
         zee = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev) if want_tables else None
         ids = torch.empty(B, H, W, dtype=torch.int32, device=dev) if want_tables else None
-        self._check(self.lib.kbe_generate_mask(_ptr(points), _ptr(shift), _i(B), _i(N), _i(int(W)), _i(int(H)), _d(float(focal)),
-                                               _d(float(baseline)), _ptr(keys, torch.int64), _ptr(winner, torch.int32), _ptr(masks),
-                                               _ptr(zee), _ptr(ids, torch.int32), _stream()), 'kbe_generate_mask')
+        self._call('kbe_generate_mask', _ptr(points), _ptr(shift), B, N, int(W), int(H), float(focal), float(baseline), _ptr(keys, torch.int64),
+                   _ptr(winner, torch.int32), _ptr(masks), _ptr(zee), _ptr(ids, torch.int32), _stream())
         return (masks, zee, ids) if want_tables else masks
 
     def generate_mask(self, points, shift, W, H, focal, baseline):
@@ -702,28 +695,26 @@ class HipKernels:
         return self.spatial_filter(masks.view(-1, 1, int(H), int(W)), 'median-5')
 
     def zkeys_clear(self, zkeys):
-        self._check(self.lib.kbe_zkeys_clear(_ptr(zkeys, torch.int32), _z(zkeys.numel()), _stream()), 'kbe_zkeys_clear')
+        self._call('kbe_zkeys_clear', _ptr(zkeys, torch.int32), zkeys.numel(), _stream())
 
     def frame_u8(self, render):
         render = _f32c(render)
         _, C, H, W = render.shape
         out = torch.empty(H, W, 3, dtype=torch.uint8, device=render.device)
-        self._check(self.lib.kbe_frame_u8(_ptr(render), _i(W), _i(H), _ptr(out, torch.uint8), _stream()), 'kbe_frame_u8')
+        self._call('kbe_frame_u8', _ptr(render), W, H, _ptr(out, torch.uint8), _stream())
         return out
 
     def crop_resize_u8(self, frame, crop_w, crop_h):
         H, W, _ = frame.shape
         out = torch.empty_like(frame)
-        self._check(self.lib.kbe_crop_resize_u8(_ptr(frame, torch.uint8), _i(W), _i(H), _i(int(crop_w)), _i(int(crop_h)),
-                                                _ptr(out, torch.uint8), _stream()), 'kbe_crop_resize_u8')
+        self._call('kbe_crop_resize_u8', _ptr(frame, torch.uint8), W, H, int(crop_w), int(crop_h), _ptr(out, torch.uint8), _stream())
         return out
 
     # -- Motion-JPEG and PNG on the device -----------------------------------------------
     def encode_raw(self, fmt, pointers, n, W, H, stride, own, scratch, out, cap, offsets, status):
         """kbe_<fmt>_encode as it is (include/kbe.h, the encoders' common contract), on the current stream: addresses, not tensors; `own`: the
         entry's integers between the stride and the scratch (the quality, the flags).  -> its return code."""
-        return getattr(self.lib, 'kbe_%s_encode' % fmt)(pointers, _i(n), _i(W), _i(H), _i(stride), *[_i(v) for v in own], ctypes.c_void_p(scratch), ctypes.c_void_p(out), _z(cap),
-                                                        ctypes.c_void_p(offsets), ctypes.c_void_p(status), _stream())
+        return self._raw('kbe_%s_encode' % fmt, pointers, n, W, H, stride, *own, scratch, out, cap, offsets, status, _stream())
 
     def _encode(self, fmt, frames, own, cap, first_guess):
         """The whole of a tensor-level call of kbe_<fmt>_encode: -> the bytes of each frame."""
@@ -733,7 +724,7 @@ class HipKernels:
         base, step = _ptr(frames, torch.uint8).value, H * W * 3
         pointers = (ctypes.c_void_p * n)(*[base + i * step for i in range(n)])
         device = frames.device
-        scratch = torch.empty((int(getattr(self.lib, 'kbe_%s_scratch_bytes' % fmt)(_i(W), _i(H), _i(n))) + 7) // 8 + 1, dtype=torch.int64, device=device)
+        scratch = torch.empty((int(getattr(self.lib, 'kbe_%s_scratch_bytes' % fmt)(W, H, n)) + 7) // 8 + 1, dtype=torch.int64, device=device)
         meta = torch.empty(n + 2, dtype=torch.int64, device=device)          # offsets [n + 1], then the status word
         cap = int(cap) if cap is not None else first_guess(n, step)
         for attempt in (0, 1):
@@ -770,16 +761,14 @@ class HipKernels:
         depth = _f32c(depth)
         B, _, H, W = depth.shape
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=depth.device)
-        self._check(self.lib.kbe_depth_to_points(_ptr(depth), _ptr(None if valid is None else _f32c(valid)), _i(B), _i(W),
-                                                 _i(H), _d(float(focal)), _ptr(out), _stream()), 'kbe_depth_to_points')
+        self._call('kbe_depth_to_points', _ptr(depth), _ptr(None if valid is None else _f32c(valid)), B, W, H, float(focal), _ptr(out), _stream())
         return out
 
     def shift_points(self, points, shift3):
         points = _f32c(points)
         B, _, N = points.shape
         out = torch.empty_like(points)
-        self._check(self.lib.kbe_shift_points(_ptr(points), _i(B), _i(N), _shift(shift3), _ptr(out), _stream()),
-                    'kbe_shift_points')
+        self._call('kbe_shift_points', _ptr(points), B, N, _shift(shift3), _ptr(out), _stream())
         return out
 
     def spatial_filter(self, x, kind):
@@ -789,8 +778,7 @@ class HipKernels:
         x = _f32c(x)
         B, C, H, W = x.shape
         out = torch.empty_like(x)
-        self._check(self.lib.kbe_spatial_filter(_ptr(x), _i(B * C), _i(W), _i(H), _i(code), _ptr(out), _stream()),
-                    'kbe_spatial_filter')
+        self._call('kbe_spatial_filter', _ptr(x), B * C, W, H, code, _ptr(out), _stream())
         return out
 
     def laplacian_valid(self, disparity, scale, threshold):
@@ -799,8 +787,7 @@ class HipKernels:
         B, C, H, W = x.shape
         out = torch.empty_like(x)
         scale = _f32c(scale).reshape(1)
-        self._check(self.lib.kbe_laplacian_valid(_ptr(x), _ptr(scale), _i(B * C), _i(W), _i(H), _f(float(threshold)), _ptr(out),
-                                                 _stream()), 'kbe_laplacian_valid')
+        self._call('kbe_laplacian_valid', _ptr(x), _ptr(scale), B * C, W, H, float(threshold), _ptr(out), _stream())
         return out
 
     def prelu_mask(self, x, slope, mask=None, out=None):
@@ -810,8 +797,7 @@ class HipKernels:
         if mask is not None and tuple(mask.shape) != (B, 1, H, W):
             raise KbeError('prelu_mask: the mask must be [B,1,H,W] = %s, got %s' % ((B, 1, H, W), tuple(mask.shape)))
         out = torch.empty_like(x) if out is None else out
-        self._check(self.lib.kbe_prelu_mask(_ptr(x), _ptr(_f32c(slope)), _ptr(None if mask is None else _f32c(mask)), _i(B), _i(C), _i(H), _i(W), _ptr(out),
-                                            _stream()), 'kbe_prelu_mask')
+        self._call('kbe_prelu_mask', _ptr(x), _ptr(_f32c(slope)), _ptr(None if mask is None else _f32c(mask)), B, C, H, W, _ptr(out), _stream())
         return out
 
     def bias_act(self, x, bias=None, slope=None, res1=None, res2=None, out=None):
@@ -822,8 +808,8 @@ class HipKernels:
         out = torch.empty_like(x) if out is None else out
         res1, res2 = (None if r is None else _f32c(r) for r in (res1, res2))
         assert all(r is None or r.shape == x.shape for r in (res1, res2))
-        self._check(self.lib.kbe_bias_act(_ptr(x), _ptr(None if bias is None else _f32c(bias)), _ptr(None if slope is None else _f32c(slope)), _ptr(res1), _ptr(res2),
-                                          _i(B), _i(C), _i(H), _i(W), _ptr(out), _stream()), 'kbe_bias_act')
+        self._call('kbe_bias_act', _ptr(x), _ptr(None if bias is None else _f32c(bias)), _ptr(None if slope is None else _f32c(slope)), _ptr(res1),
+                   _ptr(res2), B, C, H, W, _ptr(out), _stream())
         return out
 
     def upsample2x_act(self, x, slope=None):
@@ -831,7 +817,7 @@ class HipKernels:
         assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
         B, C, H, W = x.shape
         out = torch.empty(B, C, 2 * H, 2 * W, dtype=torch.float32, device=x.device)
-        self._check(self.lib.kbe_upsample2x_act(_ptr(x), _ptr(None if slope is None else _f32c(slope)), _i(B), _i(C), _i(H), _i(W), _ptr(out), _stream()), 'kbe_upsample2x_act')
+        self._call('kbe_upsample2x_act', _ptr(x), _ptr(None if slope is None else _f32c(slope)), B, C, H, W, _ptr(out), _stream())
         return out
 
     pconv_epilogue_adds_bias = True         # (PartialConv2d.forward: run the convolution without its bias)
@@ -854,12 +840,9 @@ class HipKernels:
         if residual is not None:
             residual = _f32c(residual)
             assert residual.shape == raw.shape
-        self._check(self.lib.kbe_pconv_epilogue(_ptr(raw), _ptr(None if bias is None else _f32c(bias)), _ptr(mask), _i(Cm), _i(B),
-                                                _i(Cin), _i(H), _i(W), _i(Cout), _i(Ho), _i(Wo), _i(int(kernel_size)),
-                                                _i(int(stride)), _i(int(padding)), _ptr(out), _ptr(um),
-                                                _ptr(None if act_slope is None else _f32c(act_slope)), _ptr(residual),
-                                                _i(1 if raw_without_bias and bias is not None else 0), _stream()),
-                    'kbe_pconv_epilogue')
+        self._call('kbe_pconv_epilogue', _ptr(raw), _ptr(None if bias is None else _f32c(bias)), _ptr(mask), Cm, B, Cin, H, W, Cout, Ho, Wo,
+                   int(kernel_size), int(stride), int(padding), _ptr(out), _ptr(um), _ptr(None if act_slope is None else _f32c(act_slope)),
+                   _ptr(residual), 1 if raw_without_bias and bias is not None else 0, _stream())
         return out, um
 
 

@@ -176,6 +176,7 @@ class Pipeline():
 
 WRITER_THREADS = None        # host threads the writers encode on (None: one per core, at most 32; KBE_WRITER_THREADS overrides; 1: the caller's thread only)
 _JPEG_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libkbe_jpeg.so')
+_JPEG_HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'kbe_jpeg.h')
 _jpeg_lib = None
 
 
@@ -202,11 +203,9 @@ def jpeg_encoder():
             import warnings
             warnings.warn('%s is missing (python -c "import __graft_entry__ as g; g.build()"): the video writer encodes with Pillow, one frame at a time' % _JPEG_LIB_PATH)
             return 'pillow', None
-        lib = ctypes.CDLL(_JPEG_LIB_PATH)
-        lib.kbe_jpeg_bound.restype = ctypes.c_size_t
-        lib.kbe_jpeg_bound.argtypes = [ctypes.c_int, ctypes.c_int]
-        lib.kbe_jpeg_encode_batch.restype = ctypes.c_int
-        _jpeg_lib = lib
+        from . import _cabi
+        with open(_JPEG_HEADER_PATH) as f:
+            _jpeg_lib = _cabi.bind(ctypes.CDLL(_JPEG_LIB_PATH), _cabi.prototypes(f.read(), 'KBE_JPEG_API'))
     return 'native', _jpeg_lib
 
 
@@ -332,7 +331,7 @@ def _jpegs(frames_rgb, quality):
             n = len(part)
             got = (ctypes.c_size_t * n)()
             rc = lib.kbe_jpeg_encode_batch((ctypes.c_void_p * n)(*[a.ctypes.data for a in part]), n, w, h, 3 * w, int(quality),
-                                           (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs[:n]]), ctypes.c_size_t(cap), got, _writer_pool_size(n))
+                                           (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs[:n]]), cap, got, _writer_pool_size(n))
             if rc != 0:
                 raise RuntimeError('kbe_jpeg_encode_batch: %d' % rc)
             encoded += [outs[i][:got[i]].tobytes() for i in range(n)]

@@ -20,11 +20,7 @@ OWN = {'kbe_mjpeg_encode': 'bad stride, quality or flags', 'kbe_png_encode': 'ba
 @pytest.fixture(scope='module')
 def lib():
     from ken_burns_effect_amd import _native
-    lib = ctypes.CDLL(_native.LIB_PATH)
-    for name in ('kbe_mjpeg_bound', 'kbe_png_bound', 'kbe_mjpeg_scratch_bytes', 'kbe_png_scratch_bytes'):
-        getattr(lib, name).restype = ctypes.c_size_t
-    lib.kbe_last_error.restype = ctypes.c_char_p
-    return lib
+    return _native.load()
 
 
 @pytest.mark.parametrize('row', SIZES, ids=lambda r: '%dx%dx%d' % r[:3])

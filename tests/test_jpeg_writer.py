@@ -19,10 +19,9 @@ LIB = os.path.join(ROOT, 'ken-burns-effect_amd', 'csrc', 'libkbe_jpeg.so')
 @pytest.fixture(scope='module')
 def lib():
     assert os.path.exists(LIB), 'libkbe_jpeg.so is not built: python -c "import __graft_entry__ as g; g.build()"'
-    so = ctypes.CDLL(LIB)
-    so.kbe_jpeg_bound.restype = ctypes.c_size_t
-    so.kbe_jpeg_bound.argtypes = [ctypes.c_int, ctypes.c_int]
-    return so
+    from ken_burns_effect_amd import _cabi
+    with open(os.path.join(ROOT, 'include', 'kbe_jpeg.h')) as f:
+        return _cabi.bind(ctypes.CDLL(LIB), _cabi.prototypes(f.read(), 'KBE_JPEG_API'))
 
 
 def encode(lib, frame, quality=92, cap=None):

@@ -20,7 +20,7 @@ for crop in [int(v) for v in os.environ.get('CROPS', '%d,%d' % (size * 921 // 10
     out = K.crop_resize_u8(frame, crop, crop)
     want = out.clone()
     # (the launch takes less than a call through the Python binding: the C entry point with its arguments prepared)
-    args = (_native._ptr(frame, torch.uint8), _native._i(size), _native._i(size), _native._i(crop), _native._i(crop), _native._ptr(out, torch.uint8), _native._stream())
+    args = (_native._ptr(frame, torch.uint8), size, size, crop, crop, _native._ptr(out, torch.uint8), _native._stream())
     fn = K.lib.kbe_crop_resize_u8
     ts = []
     for _ in range(5):
