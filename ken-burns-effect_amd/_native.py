@@ -324,7 +324,7 @@ class HipKernels:
         if tiled is None:
             # the tile renderer's size limits (include/kbe.h); beyond them the stage-by-stage HIP kernels take over
             tiled = (os.environ.get('KBE_RENDER_TILED', '1') != '0' and N <= (1 << 30) and int(W) * int(H) <= (1 << 30)
-                     and int(W) < (1 << 24) and int(H) < (1 << 24))
+                     and int(W) < (1 << 23) and int(H) < (1 << 23))
         if tiled:
             W, H = int(W), int(H)
             key = (dev, W, H)

@@ -728,8 +728,9 @@ int kbe_frame_scratch_init_sets(void* scratch, size_t stride, int n, int W, int 
 }  // extern "C"
 
 namespace {
-// the frame sizes the routes take (include/kbe.h): pixel offsets in 32 bits, coordinates through 24-bit multiplies
-bool frame_size_ok(int W, int H) { return W > 0 && H > 0 && (size_t) W * H <= (1u << 30) && W < (1 << 24) && H < (1 << 24); }
+// the frame sizes the routes take (include/kbe.h): pixel offsets in 32 bits, coordinates through 24-bit multiplies -- SIGNED ones
+// among them (k_project's z-splat index, __mul24(cy, cam.W)), which read a factor of 2^23 or more as negative
+bool frame_size_ok(int W, int H) { return W > 0 && H > 0 && (size_t) W * H <= (1u << 30) && W < (1 << 23) && H < (1 << 23); }
 
 // the scratch sets of a group of `n` frames (and their frames and turns, where given): non-null, 16-byte aligned, turns >= 0, no set
 // used twice.  KBE_OK, or KBE_E_INVALID with `bad` or `twice` as the error.

@@ -30,14 +30,15 @@ Dirs fill_dirs()                            // common.py:859-867, as kbe_fill.h'
 uint32_t g_seed = 12345;
 uint32_t rnd() { return (g_seed = g_seed * 1664525u + 1013904223u) >> 8; }
 
-// starts 0..9000 (+ offs[d], if given), twelve legs of up to 250 steps of us[d] in either sense: the walk as the kernel takes it against
+// starts 0..11000 -- the longest side the tables take (fill_tables_fit), every start of the binade that begins at 8192 and of the
+// tables' last 16 pixels among them -- (+ offs[d], if given), twelve legs of up to 250 steps of us[d] in either sense: the walk as the kernel takes it against
 // the additions one at a time
 struct AdvanceCounts { long walks, advances, catch_ups, bad; };
 bool sweep_advance(const float* us, const float* offs, int n_us, AdvanceCounts& n)
 {
     long& walks = n.walks; long& advances = n.advances; long& catch_ups = n.catch_ups; long& bad = n.bad;
     for (int d = 0; d < n_us; d++) {
-        for (int sub = 0; sub < 2; sub++) for (int start = 0; start < 9000; start += (start < 1100 ? 1 : 7)) {
+        for (int sub = 0; sub < 2; sub++) for (int start = 0; start <= 11000; start += (start < 1100 || (start >= 8176 && start < 8208) || start >= 10984 ? 1 : 7)) {
             const float u = us[d], first = (float) start + (offs ? offs[d] : 0.0f);
             Axis A = axis_enter(first, u, sub);
             volatile float seq = first;

@@ -72,7 +72,9 @@ CASES.update({'quality_%d' % q: (photo_like, (48, 64), q, 1) for q in QUALITIES}
 CASES.update({'noise': (noise, (64, 80), 100, 5),                   # stuffed bytes, blocks without EOB
               'checkerboard': (checkerboard, (32, 48), 100, 0),     # DC category 11
               'speck': (speck, (48, 64), 50, 0),                    # ZRL
-              'rst_wrap': (photo_like, (13, 1125), 92, 7)})         # 71 MCUs: more than 8 intervals and a short last one for any R in 2..8
+              'rst_wrap': (photo_like, (13, 1125), 92, 7),          # 71 MCUs: more than 8 intervals and a short last one for any R in 2..8
+              'widest': (photo_like, (2, 65535), 92, 4),            # the sides' limit (include/kbe.h): 4096 MCUs in one row ...
+              'tallest': (photo_like, (65535, 2), 92, 4)})          # ... and 4096 rows of one MCU (beyond libjpeg's 65500: held to the twin, and the twin's two orders to each other)
 
 
 @functools.lru_cache(maxsize=None)

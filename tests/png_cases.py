@@ -127,7 +127,11 @@ CASES.update({'one_segment': (photo_like, (64, 85), 2),             # 64 rows of
               'noise': (noise, (100, 80), 5),                       # every segment stored: the file is as long as the bound
               'stripes': (stripes, (16, 436), 0),
               'fibonacci': (fibonacci, (3, 1820), 0),                  # the length limit cuts the literal/length code
-              'photo_like': (photo_like, (128, 160), 1)})
+              'photo_like': (photo_like, (128, 160), 1),
+              'row_one_segment': (photo_like, (3, 5461), 2),        # a row of 1 + 3 * 5461 bytes is exactly SEGMENT: every segment is one row
+              'row_past_segment': (photo_like, (3, 5462), 2),       # ... and a row of SEGMENT + 3 bytes: every row crosses a segment's end, at another place
+              'widest': (photo_like, (2, 65535), 4),                # the sides' limit (include/kbe.h): 12 segments per row
+              'tallest': (photo_like, (65535, 2), 4)})              # ... and 2340 rows per segment
 
 
 @functools.lru_cache(maxsize=None)

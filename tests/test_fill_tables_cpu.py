@@ -51,6 +51,9 @@ def test_many_fp32_additions_at_once_equal_the_additions_one_at_a_time(checker):
     assert out.returncode == 0, out.stdout[-2000:]
     m = re.search(r'walks (\d+), advances (\d+) \(catch-ups (\d+)\), mismatches (\d+)', out.stdout)
     assert m and int(m.group(4)) == 0 and int(m.group(2)) > 1000000 and int(m.group(3)) > 100000, out.stdout[-500:]
+    # the walks start at 0 .. 11000, the longest side the tables take: every pixel up to 1100, around 8192 -- where a binade begins -- and
+    # of the last dozen, every seventh between; 32 steps in either sense (with starts up to 9000 only they were 142 656 walks)
+    assert int(m.group(1)) == 32 * 2 * (1100 + 1011 + 31 + 397 + 14)
     t = re.search(r'ties: walks (\d+), advances (\d+) \(catch-ups (\d+)\), mismatches (\d+)', out.stdout)       # steps that round to even
     assert t and int(t.group(4)) == 0 and int(t.group(2)) > 1000000, out.stdout[-500:]
 
@@ -102,7 +105,8 @@ def ceil_div(a, b):
 
 def test_fill_plan_follows_the_stage_bits_and_the_frame_size(checker):
     """launch_fill's decisions by the written rule (include/kbe.h: KBE_STAGE_FILL_*)."""
-    sizes = [(512, 512), (1024, 1024), (2048, 2048), (1000, 562), (12000, 512), (40, 30)]
+    sizes = [(512, 512), (1024, 1024), (2048, 2048), (1000, 562), (12000, 512), (40, 30),
+             (40, 8192), (40, 8208), (33, 11000), (33, 11001), (16416, 48)]           # (tests/elongated_cases.py: either side of 512 tile rows and of 11 000 pixels)
     cases = []
     for (W, H), bits in itertools.product(sizes, itertools.product((0, 1), repeat=4)):
         stages = sum(b * f for b, f in zip(bits, (PER_LANE, PER_HALFWAVE, BY_COUNT, DIST))) | 1 | 64       # other stage bits do not matter

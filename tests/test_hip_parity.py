@@ -1379,6 +1379,18 @@ def test_invalid_arguments_return_errors_not_crashes(K):
     rc = K.lib.kbe_render_frame_stages(z16, z16, z16, 1, 1 << 24, 1, ctypes.c_double(512.0), ctypes.c_double(120.0), None, z16, z16,
                                        None, None, None, None, 7, None, 0, 0, None)
     assert rc == -1 and b'kbe_render_frame' in K.lib.kbe_last_error()
+    # ... and from 2^23 on already: k_project's z-splat index is a SIGNED 24-bit multiply, which reads such a width as negative and
+    # would drop every splat below the first row.  Refused before anything is enqueued (the pointers are dummies), on every entry of the loop.
+    for W, H in ((1 << 23, 1), (1, 1 << 23), (1 << 23, 128)):
+        rc = K.lib.kbe_render_frame_stages(z16, z16, z16, 1, W, H, ctypes.c_double(512.0), ctypes.c_double(120.0), None, z16, z16,
+                                           None, None, None, None, 7, None, 0, 0, None)
+        assert rc == -1 and b'kbe_render_frame' in K.lib.kbe_last_error(), (W, H)
+        rc = K.lib.kbe_render_frame_fused(z16, 64, ctypes.c_double(512.0), W, H, ctypes.c_double(512.0), ctypes.c_double(120.0), None, z16, z16,
+                                          None, None, None, None, 7, None, -1, None)
+        assert rc == -1 and b'kbe_render_frame_fused' in K.lib.kbe_last_error(), (W, H)
+        rc = K.lib.kbe_render_pointcloud_tiled(z16, z16, 1, 4, W, H, ctypes.c_double(512.0), ctypes.c_double(120.0), None, z16, z16, z16, None)
+        assert rc == -1 and b'kbe_render_pointcloud_tiled' in K.lib.kbe_last_error(), (W, H)
+    assert K.lib.kbe_frame_scratch_bytes((1 << 23) - 1, 1, 0) > 0                       # (the size query itself sets no limit)
     # the packed cloud's route addresses a point's 16 bytes by a 32-bit byte offset: clouds of more than 2^28 points are refused
     # there (the plain cloud's route takes them: _native.FUSED_MAX_POINTS)
     rc = K.lib.kbe_render_frame_fused(z16, (1 << 28) + 64, ctypes.c_double(512.0), 64, 64, ctypes.c_double(512.0), ctypes.c_double(120.0), None, z16, z16,

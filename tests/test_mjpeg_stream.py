@@ -92,7 +92,7 @@ def test_inputs_that_reach_the_rare_paths():
     assert stats['rstwrap'] > 0 and len(markers) > 8 and markers[8] == 0 and (R == 1 or 71 % R != 0)
 
 
-@pytest.mark.parametrize('name', ['size_50x37', 'noise', 'checkerboard', 'speck', 'rst_wrap', 'quality_10'])
+@pytest.mark.parametrize('name', ['size_50x37', 'noise', 'checkerboard', 'speck', 'rst_wrap', 'quality_10', 'widest', 'tallest'])
 def test_blocks_coded_on_their_own_and_joined_give_the_same_bytes(name):
     """The kernels code the blocks of an interval side by side -- each block's bits packed into words of their own -- and join them
     afterwards: the same functions in that order on the CPU give the stream of the straight run, counters included."""
