@@ -162,8 +162,8 @@ KBE_API int kbe_fill_disocclusion(const float* input, const float* depth, int B,
  *          with 12 bytes per point for kbe_render_frame_fused; 0 when only the bucket route is used), initialised ONCE with
  *          kbe_frame_scratch_init;
  *          every kbe_render_frame call leaves it ready for the next one.
- *   frame_u8      [H,W,3]   out
- *   render_f32    [4,H,W]   optional: the filled float render (parity checks)
+ *   frame_u8      [H,W,3]   out; at any byte address (rows leave as 16-byte words or dwords only where the frame's own alignment allows it)
+ *   render_f32   [4,H,W]   optional: the filled float render (parity checks)
  *   existing_f32  [H*W]     optional: the accumulated weight (tensorExisting)
  *   zee_f32       [H*W]     optional: the degridded z-buffer the accumulation tested against
  *   zee_pre_f32   [H*W]     optional: the z-buffer before degrid (bit-exact contract)

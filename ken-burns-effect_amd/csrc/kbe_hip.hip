@@ -494,7 +494,7 @@ __device__ __forceinline__ void crop_resize_body(const uint8_t* __restrict__ img
             const int r = i / Q, k = i - r * Q;
             if (by + r < H) ((uint4*) (out + ((size_t) (by + r) * W + bx) * 3))[k] = ((const uint4*) s_out[r])[k];
         }
-    } else if ((W & 3) == 0 && bx + CR_TW <= W) {
+    } else if ((W & 3) == 0 && bx + CR_TW <= W && ((uintptr_t) out & 3) == 0) {
         constexpr int DW = CR_TW * 3 / 4;
         for (int i = tid; i < CR_TH * DW; i += CR_THREADS) {
             const int r = i / DW, k = i - r * DW;

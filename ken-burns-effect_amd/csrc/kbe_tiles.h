@@ -434,8 +434,9 @@ __device__ __forceinline__ void tile_epilogue(const Args& a, LDS& L, PixAcc (&ac
         for (int w = 0; w < TILE_THREADS / 64; w++) cb |= (uint32_t) sb[64 + w];
         a.coarse[tile] = cb;
     }
-    // uint8 rows leave as dwords when the row segment is 4-byte aligned and complete
-    const bool dword_rows = (W & 3) == 0 && (TW * 3) % 4 == 0 && x0 + TW <= W;
+    // uint8 rows leave as dwords when the row segment is 4-byte aligned -- the frame pointer included: a caller may hold a frame at any
+    // byte (tests/test_hip_guarded.py) -- and complete
+    const bool dword_rows = (W & 3) == 0 && (TW * 3) % 4 == 0 && x0 + TW <= W && ((uintptr_t) a.frame & 3) == 0;
     if ((W & 15) == 0 && (TW * 3) % 16 == 0 && x0 + TW <= W && ((uintptr_t) a.frame & 15) == 0) {
         // ... as 16-byte words where the row segments are 16-byte aligned (a tile row is 96 bytes: six of them): 96 stores for the
         // tile, by the workgroup's LAST threads (the z decode in front of the degrid is the first threads' work) -- a trip for 96

@@ -10,8 +10,7 @@ import torch
 
 import mjpeg_cases as mc
 import png_cases as pc
-
-SENTINEL, GUARD = 0xA5, 4096
+from guarded import GUARD, SENTINEL, Guard           # (0xA5, 4096: the bands of the output buffer here are the harness's)
 
 # fmt: kbe_<fmt>_encode, kbe_<fmt>_scratch_bytes, kbe_<fmt>_bound; cases: the CPU suite's module (CASES, case_frames, case_twin, BGR); own(name): the
 # entry's arguments in front of the flags for that case; encode(K, frames, name, **kw): the tensor-level call; ladder: the case of the
@@ -37,18 +36,22 @@ def on_device(frames):
 def run(K, enc, frames, own, cap, W=None, stride=None, n=None, status_before=7, shift=0):
     """The entry on a uint8 device tensor [n,H,Wt,3] (W <= Wt: the rows' stride is Wt's) with a buffer of `cap` bytes (`shift` bytes off its
     allocation's start) followed by GUARD bytes, everything the call may write filled with sentinels first; own: the entry's integers up to
-    the flags.  -> (rc, offsets, status, the buffer with its guard)."""
+    the flags.  The scratch is exactly kbe_<fmt>_scratch_bytes, rounded up only to the 8 bytes its alignment check asks for, every byte of
+    it 0xFF, between two guard bands of its own (tests/guarded.py) that the call must leave alone.  -> (rc, offsets, status, the buffer
+    with its guard)."""
     count, H, Wt, _ = frames.shape
     W = Wt if W is None else W
     n = count if n is None else n
     step = H * Wt * 3
     pointers = (ctypes.c_void_p * max(n, 1))(*[frames.data_ptr() + i * step for i in range(n)])
-    scratch = torch.empty((int(getattr(K.lib, 'kbe_%s_scratch_bytes' % enc.fmt)(W, H, max(n, 1))) + 7) // 8 + 1, dtype=torch.int64, device='cuda')
+    guard = Guard(poison=0xFF)
+    scratch = guard.empty(((int(getattr(K.lib, 'kbe_%s_scratch_bytes' % enc.fmt)(W, H, max(n, 1))) + 7) // 8 * 8,), torch.uint8, 'cuda')
     out = torch.full((shift + cap + GUARD,), SENTINEL, dtype=torch.uint8, device='cuda')
     offsets = torch.full((max(n, 1) + 1,), -1, dtype=torch.int64, device='cuda')
     status = torch.full((1,), status_before, dtype=torch.int32, device='cuda')
     rc = K.encode_raw(enc.fmt, pointers, n, W, H, 3 * Wt if stride is None else stride, own, scratch.data_ptr(), out.data_ptr() + shift, cap, offsets.data_ptr(), status.data_ptr())
     torch.cuda.synchronize()
+    guard.check()
     got = out.cpu().numpy()
     assert (got[:shift] == SENTINEL).all()
     return rc, offsets.cpu().tolist(), int(status.item()), got[shift:]
