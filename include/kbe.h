@@ -32,6 +32,10 @@
  * Numerical contract: identical to oracle/kbe_oracle.c (which is pinned bit-for-bit to the
  * reference kernel text): z-buffer and winner indices bit-exact; degrid uses the out-of-place
  * (Jacobi) schedule; accumulation order is the hardware's atomic order (last-ulp differences).
+ * The band: points farther than F*B / 475712 from the camera (0.129 at F*B = 61440) have their dblError of common.py:470 in
+ * [2^19, 1e6], where the kernels' fp32-only paths are exact; nearer ones (dblError below 2^19, negative below F*B / 1e6), depths
+ * below 16 or 2, and depths from 1e30 on leave those paths for the reference's own fp64 / IEEE expressions -- slower, and the
+ * oracle's results either way (tests/test_hip_near_field.py).
  */
 #ifndef KBE_H
 #define KBE_H

@@ -96,27 +96,75 @@ def test_render_pointcloud_whole(K, oracle, case):
     assert (np.abs(c(render) - r0.numpy()) <= 2e-5 * scale).all()
 
 
+def _random_focal_baseline_pairs():
+    """Eight (F, B) with F * B in 10^[-2, 9] (fixed seed), B a float or an int as the draw has it; most products are not fp32 values."""
+    rng = np.random.default_rng(470)
+    pairs = []
+    for k, exponent in enumerate(rng.permutation(np.linspace(-2.0, 9.0, 8))):
+        baseline = int(rng.integers(1, 400)) if k % 2 else float(rng.uniform(0.01, 400.0))
+        fb = 10.0 ** (exponent + rng.uniform(-0.4, 0.4))
+        pairs.append((float(min(max(fb, 0.01), 1e9) / baseline), baseline))
+    assert sum(float(np.float32(f * b)) != f * b for f, b in pairs) >= 4
+    return pairs
+
+
+def _dbl_error_depths(fb, n_random, n_boundary, rng):
+    """Depths for the division-free dblError: random ones, tiny / huge ones, the floats around the fp32 rounding boundaries of
+    1e6 - fb / z for THIS fb, and the floats around 16.0 (project_err_fast: pz >= 16)."""
+    zs = [rng.uniform(16.0, 60000.0, n_random), rng.uniform(0.001, 20.0, n_random // 20), 10.0 ** rng.uniform(-3, 7, n_random // 20)]
+    # boundaries: Q = (n + 0.5) / 16  <=>  z = fb / Q - 1e-7; take the floats around each
+    n = rng.integers(1, 16 * 4000, n_boundary).astype(np.float64)
+    zb = (fb / ((n + 0.5) / 16.0) - 1e-7).astype(np.float32)
+    for start in (zb, np.full(1, 16.0, np.float32)):
+        for k in range(-3, 4):
+            z = start.copy()
+            for _ in range(abs(k)):
+                z = np.nextafter(z, np.float32(np.inf if k > 0 else -np.inf))
+            zs.append(z)
+    return np.concatenate([np.asarray(v, dtype=np.float32) for v in zs])
+
+
+def _fast_dbl_error_is_exact(K, focal, baseline, n_random=4_000_000, n_boundary=300_000):
+    fb = focal * baseline
+    z = _dbl_error_depths(fb, n_random, n_boundary, np.random.default_rng(11))
+    fast, exact = K.selftest_err(torch.from_numpy(z).cuda(), focal, baseline)
+    with np.errstate(over='ignore'):
+        want = (1000000.0 - fb / (z.astype(np.float64) + 0.0000001)).astype(np.float32)
+    assert_bits_equal(c(exact), want, 'fp64 expression on the GPU vs numpy')
+    assert_bits_equal(c(fast), want, 'fast path')
+    return z
+
+
 @pytest.mark.parametrize('focal,baseline', [(512.0, 120), (409.6, 120), (153.60000000000002, 40.0), (192.0, 120)])
 def test_fast_dbl_error_is_exact(K, focal, baseline):
     """The division-free dblError of the frame loop against the literal fp64 expression (on the GPU and in
     numpy): random depths, tiny / huge depths, and depths placed right on the fp32 rounding boundaries of
     1e6 - F*B/z (where the fast path must notice that it cannot decide and fall back)."""
-    rng = np.random.default_rng(11)
-    fb = focal * baseline
-    zs = [rng.uniform(16.0, 60000.0, 4_000_000), rng.uniform(0.001, 20.0, 200_000), 10.0 ** rng.uniform(-3, 7, 200_000)]
-    # boundaries: Q = (n + 0.5) / 16  <=>  z = fb / Q - 1e-7; take the floats around each
-    n = rng.integers(1, 16 * 4000, 300_000).astype(np.float64)
-    zb = (fb / ((n + 0.5) / 16.0) - 1e-7).astype(np.float32)
-    for k in range(-3, 4):
-        z = zb.copy()
-        for _ in range(abs(k)):
-            z = np.nextafter(z, np.float32(np.inf if k > 0 else -np.inf))
-        zs.append(z)
-    z = np.concatenate([np.asarray(v, dtype=np.float32) for v in zs])
-    fast, exact = K.selftest_err(torch.from_numpy(z).cuda(), focal, baseline)
-    want = (1000000.0 - fb / (z.astype(np.float64) + 0.0000001)).astype(np.float32)
-    assert_bits_equal(c(exact), want, 'fp64 expression on the GPU vs numpy')
-    assert_bits_equal(c(fast), want, 'fast path')
+    _fast_dbl_error_is_exact(K, focal, baseline)
+
+
+# B as a float and as an int; products over 10^[-2, 9]; F * B >= 7.6e6 * 16 (depths from 16 on leave the fast path through s >= 7.6e6); F * B < 1
+WIDER_PAIRS = [(512.0, 120.0), (409.6, 120.0), (153.60000000000002, 40)] + _random_focal_baseline_pairs() + [(4096.0, 30000.0), (0.5, 1.5), (0.5, 1)]
+
+
+@pytest.mark.parametrize('focal,baseline', WIDER_PAIRS, ids=['%.6g-%r' % (f, round(b, 3)) for f, b in WIDER_PAIRS])
+def test_fast_dbl_error_is_exact_at_other_products(K, focal, baseline):
+    """The same at (F, B) pairs beyond the synthetic scenes' (test_fast_dbl_error_is_exact's assertions, about a million depths each)."""
+    z = _fast_dbl_error_is_exact(K, focal, baseline, n_random=700_000, n_boundary=40_000)
+    assert 900_000 < z.size < 1_200_000
+    if focal * baseline >= 7600000.0 * 16.0:
+        assert (16.0 * np.float32(focal * baseline) / z[z >= 16.0] >= np.float32(7600000.0)).sum() > 1000
+
+
+def test_fast_dbl_error_is_exact_at_the_focals_of_a_dolly(K):
+    """... and at the focals common.frame_cameras hands the frames of a dolly zoom (common._camera_at: a different one per step)."""
+    from ken_burns_effect_amd import common
+    settings, oc = _scene((256, 256), dolly=True)
+    cams = common.frame_cameras(dict(settings, dblSteps=[0.0, 0.25, 0.5, 0.75, 1.0]), oc)
+    focals = [focal for focal, _ in cams]
+    assert len(set(focals)) == 5
+    for focal in focals:
+        _fast_dbl_error_is_exact(K, focal, oc['dblBaseline'], n_random=700_000, n_boundary=40_000)
 
 
 def test_unscaled_division_is_the_ieee_division(K):
