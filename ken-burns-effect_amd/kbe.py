@@ -7,6 +7,7 @@
         [--allow-random-weights]                       (new: render with seeded weights where a checkpoint is missing instead of failing)
         [--jpeg native|pillow|device]                  (new: who encodes a Motion-JPEG video's frames -- host threads, Pillow, or the GPU: env KBE_JPEG)
         [--png native|device]                          (new: who encodes the PNG frames of --write-frames -- host threads or the GPU: env KBE_PNG)
+        [--gif] [--gif-dither none|ordered]            (new: also write 3d_kbe.gif, an animated GIF encoded on the GPU: env KBE_GIF=1, KBE_GIF_DITHER)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -19,12 +20,12 @@ import numpy as np
 import torch
 
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
-                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=']
+                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=']
 
 
 def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
-           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None,
+           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -33,12 +34,14 @@ def parse(argv):
         if name in window:
             if argument != '':
                 window[name] = int(argument)
-        elif name in ('dolly', 'write-frames', 'pretrained-refine', 'pretrained-estim', '2d', 'allow-random-weights'):
+        elif name in ('dolly', 'write-frames', 'pretrained-refine', 'pretrained-estim', '2d', 'allow-random-weights', 'gif'):
             cfg[name] = True
         elif argument != '':
             cfg[name] = argument
     if cfg['png'] not in (None, 'native', 'device'):
         raise SystemExit('--png %s: native or device' % cfg['png'])
+    if cfg['gif-dither'] not in (None, 'none', 'ordered'):
+        raise SystemExit('--gif-dither %s: none or ordered' % cfg['gif-dither'])
     return cfg, window
 
 
@@ -96,7 +99,7 @@ def main(argv=None):
     zoom = windows_for(image.shape[3], image.shape[2], window, cfg['dolly'])
     paths = [cfg['estim-path'], cfg['refine-path'], cfg['inpaint-path']] + ([cfg['inpaint-depth']] if cfg['inpaint-depth'] else [])
     pipe = Pipeline(model_paths=paths, dolly=cfg['dolly'], output_frames=cfg['write-frames'], pretrain=cfg['pretrained-refine'], d2=cfg['2d'],
-                    semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None)
+                    semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'])
     frames = pipe(image, zoom, cfg['out'], pretrained_estim=cfg['pretrained-estim'])
     print('%d frames of %dx%d written to %s' % (len(frames), image.shape[3], image.shape[2], cfg['out']))
 

@@ -28,7 +28,10 @@ from .utils import load_models, resize_image
 
 class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
-                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None):
+                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None):
+        # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
+        # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before
+        self.gif, self.gif_dither = gif, gif_dither
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -141,7 +144,11 @@ class Pipeline():
             # route below
             jpeg_on_device = output_path is not None and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
             png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
-            on_device = png_on_device or (jpeg_on_device and not self.output_frames)
+            video_from_hbm = jpeg_on_device and (png_on_device or not self.output_frames)
+            # KBE_GIF=1 (Pipeline(gif=True), kbe.py --gif): the frames stay in HBM as well and 3d_kbe.gif is encoded from them (gif.py);
+            # every other file is then written as it would have been without the switch, by the same route's encoder
+            gif_on = output_path is not None and gif_switch(getattr(self, 'gif', None))
+            on_device = png_on_device or video_from_hbm or gif_on
             frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                               'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                               'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device)
@@ -151,15 +158,22 @@ class Pipeline():
             if png_on_device:
                 from . import _native
                 write_frames(os.path.join(output_path, 'frames'), None, pngs=_native.kernels().png_encode(frames, bgr=not pretrained_estim))
-            if jpeg_on_device:
+            if gif_on:
+                from . import gif
+                gif.write_gif(os.path.join(output_path, '3d_kbe.gif'), frames, fps=25, bgr=not pretrained_estim, dither=gif_dither(getattr(self, 'gif_dither', None)))
+            if video_from_hbm:
                 encoded = jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=not pretrained_estim)
                 # forth and back (:131): every distinct frame was encoded once, the way back is the same byte objects again
                 write_video(os.path.join(output_path, '3d_kbe.mp4'), None, fps=25, jpegs=encoded + encoded[-2::-1], frame_size=tuple(frames.shape[1:3]))
-            host = frames.cpu().numpy()                                                 # the return value (with jpeg_on_device: fetched after the video is written)
+            host = frames.cpu().numpy()                                                 # the return value (with video_from_hbm: fetched after the video is written)
             out = [host[i] for i in range(host.shape[0])]
-            if not jpeg_on_device:
+            png_on_host = bool(self.output_frames) and not png_on_device               # (only with the GIF: the PNG frames from the fetched frames, as without it)
+            if png_on_host or not video_from_hbm:
                 rgb = out if pretrained_estim else [f[:, :, ::-1] for f in out]
-                write_video(os.path.join(output_path, '3d_kbe.mp4'), rgb + rgb[-2::-1], fps=25)
+                if png_on_host:
+                    write_frames(os.path.join(output_path, 'frames'), rgb)
+                if not video_from_hbm:
+                    write_video(os.path.join(output_path, '3d_kbe.mp4'), rgb + rgb[-2::-1], fps=25)
             return out
         if output_path is not None:
             os.makedirs(output_path, exist_ok=True)
@@ -245,6 +259,19 @@ def png_encoder():
     kind = os.environ.get('KBE_PNG', 'native')
     if kind not in ('native', 'device'):
         raise ValueError('KBE_PNG=%s: native or device' % kind)
+    return kind
+
+
+def gif_switch(gif=None):
+    """Whether 3d_kbe.gif is written beside the video: what Pipeline was told, else env KBE_GIF=1 (kbe.py --gif).  Off by default."""
+    return bool(gif) if gif is not None else os.environ.get('KBE_GIF', '0') == '1'
+
+
+def gif_dither(kind=None):
+    """The GIF's dither: 'ordered' (an 8 x 8 Bayer matrix of one 5-bit step, the default) or 'none'; env KBE_GIF_DITHER, kbe.py --gif-dither."""
+    kind = kind or os.environ.get('KBE_GIF_DITHER', 'ordered')
+    if kind not in ('none', 'ordered'):
+        raise ValueError('KBE_GIF_DITHER=%s: none or ordered' % kind)
     return kind
 
 

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Frames that lie in HBM -> Motion-JPEG streams (--format mjpeg) or the PNG files of --write-frames (--format png) in host memory, two ways
-in the SAME run, taking turns:
+"""Frames that lie in HBM -> Motion-JPEG streams (--format mjpeg), the PNG files of --write-frames (--format png) or an animated GIF (--format
+gif) in host memory, two ways in the SAME run, taking turns:
   device: HipKernels.mjpeg_encode / png_encode (kbe_mjpeg_encode, kbe_png_encode: the GPU encodes, the streams or files cross the link);
+          gif: what gif.write_gif does short of the file -- histogram, palette (host), table, kbe_gif_encode, assemble;
   host:   the frames cross the link raw into pinned memory and the writers' host threads encode them (mjpeg: libkbe_jpeg.so,
-          kbe_jpeg_encode_batch; png: pipeline.png_bytes, zlib level 1).
+          kbe_jpeg_encode_batch; png: pipeline.png_bytes, zlib level 1; gif: Pillow's save(format='GIF', save_all=True), one thread).
 Wall clock around calls that end with the bytes on the host (the device's ends in a device synchronise), every arm warmed up, SECONDS per
 arm and size.  One JSON line per size on stdout and, with --out, in a file.  --profile: nothing but ROUNDS device encodes of each size
 (for a `rocprofv3 --kernel-trace --stats` run of its own).  Needs a GPU."""
@@ -20,7 +21,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ken_burns_effect_amd import _native, pipeline  # noqa: E402
+from ken_burns_effect_amd import _native, gif, pipeline  # noqa: E402
 
 
 def photo_like(n, size, device):
@@ -35,9 +36,101 @@ def photo_like(n, size, device):
     return frames
 
 
+def gif_main(args):
+    """--format gif: the device route (the whole of it, and its stages one by one with HIP events and a host clock) against raw delivery +
+    Pillow; microseconds and bytes per frame."""
+    from PIL import Image
+    lines = []
+    for spec in args.sizes.split(','):
+        size, n = (int(v) for v in spec.split('x'))
+        frames = photo_like(n, size, torch.device('cuda'))
+        pinned = torch.empty(frames.shape, dtype=torch.uint8).pin_memory()
+
+        def device_arm():
+            palette = gif.palette_from_histogram(gif.histogram(frames))
+            return gif.assemble(gif.encode(frames, gif.lut(palette), dither='ordered'), size, size, palette)
+
+        def host_arm():
+            pinned.copy_(frames, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            host = pinned.numpy()
+            images = [Image.fromarray(host[i]) for i in range(n)]
+            out = io.BytesIO()
+            images[0].save(out, format='GIF', save_all=True, append_images=images[1:], duration=40, loop=0)
+            return out.getvalue()
+
+        if args.profile:
+            for _ in range(args.rounds):
+                device_arm()
+            torch.cuda.synchronize()
+            continue
+        on_device, on_host = device_arm(), host_arm()                   # warm-up, and the bytes to look at
+        times = {'device': [], 'host': []}
+        while True:                                                     # taking turns; an arm stops once it has its SECONDS and three calls (Pillow takes seconds per call)
+            wanted = [(name, arm) for name, arm in (('device', device_arm), ('host', host_arm)) if sum(times[name]) < args.seconds or len(times[name]) < 3]
+            if not wanted:
+                break
+            for name, arm in wanted:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                arm()
+                torch.cuda.synchronize()
+                times[name].append(time.perf_counter() - t0)
+        # the stages of the device route
+        stages = {}
+
+        def clocked(name, work):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            result = work()
+            torch.cuda.synchronize()
+            stages.setdefault(name, []).append(1e3 * (time.perf_counter() - t0))
+            return result
+        for _ in range(5):
+            hist = clocked('histogram_ms', lambda: gif.histogram(frames))
+            palette = clocked('palette_host_ms', lambda: gif.palette_from_histogram(hist))
+            table = clocked('lut_ms', lambda: gif.lut(palette))
+            units = clocked('encode_and_fetch_ms', lambda: gif.encode(frames, table, dither='ordered'))
+            clocked('assemble_host_ms', lambda: gif.assemble(units, size, size, palette))
+        # kbe_gif_encode alone: the launches of a call on buffers that exist, HIP events
+        cap = sum(len(u) for u in units)
+        scratch = torch.empty(int(gif.load().kbe_gif_scratch_bytes(size, size, n)) // 8 + 1, dtype=torch.int64, device='cuda')
+        out = torch.empty(cap, dtype=torch.uint8, device='cuda')
+        meta = torch.empty(n + 2, dtype=torch.int64, device='cuda')
+        pointers = (ctypes.c_void_p * n)(*[frames.data_ptr() + i * size * size * 3 for i in range(n)])
+        kernel_ms = []
+        for _ in range(7):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            gif._call('kbe_gif_encode', pointers, n, size, size, 3 * size, 0, gif.DITHER['ordered'], 4, table.data_ptr(), scratch.data_ptr(), out.data_ptr(), cap, meta.data_ptr(),
+                      meta.data_ptr() + 8 * (n + 1), _native._stream())
+            e1.record()
+            torch.cuda.synchronize()
+            kernel_ms.append(e0.elapsed_time(e1))
+        shown = Image.open(io.BytesIO(on_device))
+        assert shown.n_frames == n and shown.size == (size, size)
+        first = frames[0].cpu().numpy().astype(np.float64)
+
+        def psnr(data):
+            return float(10.0 * np.log10(255.0 ** 2 / np.mean((np.asarray(Image.open(io.BytesIO(data)).convert('RGB')).astype(np.float64) - first) ** 2)))
+        med = {name: float(np.median(t)) for name, t in times.items()}
+        line = dict(what='frames in HBM -> an animated GIF on the host', size=size, frames=n, gpu=torch.cuda.get_device_name(0), raw_bytes=n * size * size * 3,
+                    device_us_per_frame=1e6 * med['device'] / n, host_us_per_frame=1e6 * med['host'] / n, device_over_host_speedup=med['host'] / med['device'],
+                    device_bytes_per_frame=len(on_device) / n, host_bytes_per_frame=len(on_host) / n, calls={name: len(t) for name, t in times.items()},
+                    device_stages_ms_per_video={name: float(np.median(t)) for name, t in stages.items()},
+                    kbe_gif_encode_kernels_only_ms_per_video={'median': float(np.median(kernel_ms)), 'min': min(kernel_ms)},
+                    first_frame_psnr_db={'device': psnr(on_device), 'host': psnr(on_host)})
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if args.out and lines:
+        with open(args.out, 'w') as f:
+            for line in lines:
+                f.write(json.dumps(line) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--format', required=True, choices=['mjpeg', 'png'])
+    ap.add_argument('--format', required=True, choices=['mjpeg', 'png', 'gif'])
     ap.add_argument('--sizes', default='512x64,1024x75', help='SIZExFRAMES, comma separated')
     ap.add_argument('--seconds', type=float, default=3.0)
     ap.add_argument('--quality', type=int, default=92, help='mjpeg')
@@ -51,6 +144,8 @@ def main():
     mjpeg = args.format == 'mjpeg'
     assert not mjpeg or pipeline.jpeg_encoder()[0] == 'native'
     own = (args.quality, 0) if mjpeg else (0,)                      # the entry's integers between the stride and the scratch
+    if args.format == 'gif':
+        return gif_main(args)
     pipeline.WRITER_THREADS = args.threads
     os.environ.pop('KBE_WRITER_THREADS', None)
     lines = []
