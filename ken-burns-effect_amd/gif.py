@@ -5,6 +5,9 @@ The device writes one UNIT per frame (graphic control extension, image descripto
 one global palette (a count-weighted median cut of the frames' RGB555 histogram, on the host: 32 768 counts) and assembles the file.  It is
 the only module that names the entries of kbe_gif.h: they are exported by libkbe_hip.so beside those of kbe.h, typed from their own header
 the way pipeline.jpeg_encoder types libkbe_jpeg.so.  No fallback: without the HIP library every call here raises.
+
+write_gif(size=, every=) writes a GIF smaller than the render and of fewer frames (``kbe.py --gif-width, --gif-fps``): the frames are reduced on
+the device first, by area.reduce (area.py binds that entry; this module names none of its).
 """
 import ctypes
 import os
@@ -202,10 +205,31 @@ def delay_for(fps):
     return max(2, int(round(100.0 / fps)))
 
 
-def write_gif(path, frames_in_hbm, fps=25, bgr=False, dither='ordered'):
+def kept_frames(n, every):
+    """The frames of n that a GIF of every `every`-th frame keeps: 0, every, 2 every, ... and the last one, so that the turn-around is the
+    clip's true end pose."""
+    every = int(every)
+    if every < 1:
+        raise ValueError('every %d: 1 (all frames) or more' % every)
+    kept = list(range(0, n, every))
+    return kept if kept[-1] == n - 1 else kept + [n - 1]
+
+
+def write_gif(path, frames_in_hbm, fps=25, bgr=False, dither='ordered', *, size=None, every=1):
     """The frames, forth and back, as an animated GIF that loops for ever: one palette for the whole clip from the frames' histogram,
     every distinct frame encoded once -- a unit holds no field that depends on its place, the way back is the same byte objects again.
+    ``size``: (w, h), neither above the frames' -- the frames are reduced on the device first (area.reduce: the exact area average; see
+    area.size_for), palette and all come from the reduced frames.  ``every``: only the frames of kept_frames are written, each shown
+    delay_for(fps / every) long.  Without the two the file is what it was before they existed.
     -> (the palette, the number of frames in the file)"""
+    if every != 1:
+        import torch
+        kept = kept_frames(int(frames_in_hbm.shape[0]), every)
+        frames_in_hbm = frames_in_hbm.index_select(0, torch.tensor(kept, device=frames_in_hbm.device))
+        fps = fps / float(every)
+    if size is not None:
+        from . import area
+        frames_in_hbm = area.reduce(frames_in_hbm, int(size[0]), int(size[1]))
     H, W = int(frames_in_hbm.shape[1]), int(frames_in_hbm.shape[2])
     palette = palette_from_histogram(histogram(frames_in_hbm, bgr=bgr))
     units = encode(frames_in_hbm, lut(palette), bgr=bgr, dither=dither, delay_cs=delay_for(fps))

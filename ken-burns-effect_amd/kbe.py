@@ -8,6 +8,8 @@
         [--jpeg native|pillow|device]                  (new: who encodes a Motion-JPEG video's frames -- host threads, Pillow, or the GPU: env KBE_JPEG)
         [--png native|device]                          (new: who encodes the PNG frames of --write-frames -- host threads or the GPU: env KBE_PNG)
         [--gif] [--gif-dither none|ordered]            (new: also write 3d_kbe.gif, an animated GIF encoded on the GPU: env KBE_GIF=1, KBE_GIF_DITHER)
+        [--gif-width N] [--gif-fps F]                  (new, with --gif: the GIF N pixels wide -- reduced on the GPU, never enlarged -- and at about F
+                                                        frames a second, every max(1, round(25 / F))-th frame: env KBE_GIF_WIDTH, KBE_GIF_FPS)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -20,12 +22,12 @@ import numpy as np
 import torch
 
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
-                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=']
+                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=']
 
 
 def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
-           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None,
+           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -42,6 +44,20 @@ def parse(argv):
         raise SystemExit('--png %s: native or device' % cfg['png'])
     if cfg['gif-dither'] not in (None, 'none', 'ordered'):
         raise SystemExit('--gif-dither %s: none or ordered' % cfg['gif-dither'])
+    for name in ('gif-width', 'gif-fps'):
+        if cfg[name] is not None and not cfg['gif']:
+            raise SystemExit('--%s %s: only with --gif' % (name, cfg[name]))
+    if cfg['gif-width'] is not None:
+        if not (cfg['gif-width'].isdigit() and int(cfg['gif-width']) >= 1):
+            raise SystemExit('--gif-width %s: a number of pixels, 1 or more' % cfg['gif-width'])
+        cfg['gif-width'] = int(cfg['gif-width'])
+    if cfg['gif-fps'] is not None:
+        try:
+            cfg['gif-fps'] = float(cfg['gif-fps'])
+        except ValueError:
+            cfg['gif-fps'] = 0.0
+        if not 0.0 < cfg['gif-fps'] < float('inf'):
+            raise SystemExit('--gif-fps: frames a second, above 0')
     return cfg, window
 
 
@@ -96,10 +112,13 @@ def main(argv=None):
         import os
         os.environ['KBE_PNG'] = cfg['png']          # (... and pipeline.png_encoder)
     image = load_image(cfg['in'], cfg['pretrained-estim'])
+    if cfg['gif-width'] is not None and cfg['gif-width'] > image.shape[3]:
+        raise SystemExit('--gif-width %d: the image is %d pixels wide, and the GIF is only ever reduced' % (cfg['gif-width'], image.shape[3]))
     zoom = windows_for(image.shape[3], image.shape[2], window, cfg['dolly'])
     paths = [cfg['estim-path'], cfg['refine-path'], cfg['inpaint-path']] + ([cfg['inpaint-depth']] if cfg['inpaint-depth'] else [])
     pipe = Pipeline(model_paths=paths, dolly=cfg['dolly'], output_frames=cfg['write-frames'], pretrain=cfg['pretrained-refine'], d2=cfg['2d'],
-                    semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'])
+                    semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'],
+                    gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'])
     frames = pipe(image, zoom, cfg['out'], pretrained_estim=cfg['pretrained-estim'])
     print('%d frames of %dx%d written to %s' % (len(frames), image.shape[3], image.shape[2], cfg['out']))
 

@@ -28,10 +28,13 @@ from .utils import load_models, resize_image
 
 class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
-                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None):
+                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
-        # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before
-        self.gif, self.gif_dither = gif, gif_dither
+        # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
+        # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
+        # gif_fps: the GIF's frame rate, every max(1, round(25 / gif_fps))-th frame and the last; env KBE_GIF_FPS.  None and no env: the
+        # frames' own size, every frame
+        self.gif, self.gif_dither, self.gif_width, self.gif_fps = gif, gif_dither, gif_width, gif_fps
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -133,6 +136,14 @@ class Pipeline():
     def _run(self, tensorImage, zoom_settings, output_path, inpaint_depth, pretrained_estim):
         from .utils import miopen_tuned_once
         auto = getattr(self, 'miopen_find', False) == 'auto'
+        # KBE_GIF=1 (Pipeline(gif=True), kbe.py --gif): the frames stay in HBM as well and 3d_kbe.gif is encoded from them (gif.py); every
+        # other file is then written as it would have been without the switch, by the same route's encoder.  Its width and rate (gif_shape)
+        # are looked at before any network runs: the frames are the image's size, and a GIF wider than them is refused
+        gif_on = output_path is not None and gif_switch(getattr(self, 'gif', None))
+        if gif_on:
+            gif_wide, gif_every = gif_shape(getattr(self, 'gif_width', None), getattr(self, 'gif_fps', None))
+            if gif_wide is not None and gif_wide > tensorImage.size(3):
+                raise ValueError('a GIF %d pixels wide from an image %d wide: the GIF is only ever reduced' % (gif_wide, tensorImage.size(3)))
         with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
             self.estimate(tensorImage)
             if inpaint_depth:
@@ -145,9 +156,6 @@ class Pipeline():
             jpeg_on_device = output_path is not None and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
             png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
             video_from_hbm = jpeg_on_device and (png_on_device or not self.output_frames)
-            # KBE_GIF=1 (Pipeline(gif=True), kbe.py --gif): the frames stay in HBM as well and 3d_kbe.gif is encoded from them (gif.py);
-            # every other file is then written as it would have been without the switch, by the same route's encoder
-            gif_on = output_path is not None and gif_switch(getattr(self, 'gif', None))
             on_device = png_on_device or video_from_hbm or gif_on
             frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                               'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
@@ -159,8 +167,10 @@ class Pipeline():
                 from . import _native
                 write_frames(os.path.join(output_path, 'frames'), None, pngs=_native.kernels().png_encode(frames, bgr=not pretrained_estim))
             if gif_on:
-                from . import gif
-                gif.write_gif(os.path.join(output_path, '3d_kbe.gif'), frames, fps=25, bgr=not pretrained_estim, dither=gif_dither(getattr(self, 'gif_dither', None)))
+                from . import area, gif
+                gif_size = None if gif_wide is None else area.size_for(frames.shape[2], frames.shape[1], width=gif_wide)
+                gif.write_gif(os.path.join(output_path, '3d_kbe.gif'), frames, fps=25, bgr=not pretrained_estim, dither=gif_dither(getattr(self, 'gif_dither', None)),
+                              size=gif_size, every=gif_every)
             if video_from_hbm:
                 encoded = jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=not pretrained_estim)
                 # forth and back (:131): every distinct frame was encoded once, the way back is the same byte objects again
@@ -273,6 +283,30 @@ def gif_dither(kind=None):
     if kind not in ('none', 'ordered'):
         raise ValueError('KBE_GIF_DITHER=%s: none or ordered' % kind)
     return kind
+
+
+def gif_shape(width=None, fps=None):
+    """(the GIF's width or None for the frames' own, every how many frames it keeps): what Pipeline was told, else env KBE_GIF_WIDTH and
+    KBE_GIF_FPS (kbe.py --gif-width, --gif-fps).  The video has 25 frames a second: a GIF of F a second keeps every max(1, round(25 / F))-th."""
+    width = width if width is not None else os.environ.get('KBE_GIF_WIDTH') or None
+    fps = fps if fps is not None else os.environ.get('KBE_GIF_FPS') or None
+    if width is not None:
+        try:
+            width = int(width)
+        except ValueError:
+            width = 0
+        if width < 1:
+            raise ValueError("the GIF's width (KBE_GIF_WIDTH, --gif-width): a number of pixels, 1 or more")
+    every = 1
+    if fps is not None:
+        try:
+            fps = float(fps)
+        except ValueError:
+            fps = 0.0
+        if not 0.0 < fps < float('inf'):
+            raise ValueError("the GIF's frame rate (KBE_GIF_FPS, --gif-fps): frames a second, above 0")
+        every = max(1, int(round(25.0 / fps)))
+    return width, every
 
 
 def write_frames(frames_dir, frames_rgb, pngs=None):

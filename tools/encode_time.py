@@ -6,7 +6,9 @@ gif) in host memory, two ways in the SAME run, taking turns:
   host:   the frames cross the link raw into pinned memory and the writers' host threads encode them (mjpeg: libkbe_jpeg.so,
           kbe_jpeg_encode_batch; png: pipeline.png_bytes, zlib level 1; gif: Pillow's save(format='GIF', save_all=True), one thread).
 Wall clock around calls that end with the bytes on the host (the device's ends in a device synchronise), every arm warmed up, SECONDS per
-arm and size.  One JSON line per size on stdout and, with --out, in a file.  --profile: nothing but ROUNDS device encodes of each size
+arm and size.  With --gif-width and/or --gif-every (--format gif), instead: the device route at the frames' own size and every frame (as above)
+against the same route at that width (area.reduce, the exact area average on the GPU, the height by area.size_for) and every so-many-th frame,
+both short of the file, and the bytes of the files they would write, forth and back.  One JSON line per size on stdout and, with --out, in a file.  --profile: nothing but ROUNDS device encodes of each size
 (for a `rocprofv3 --kernel-trace --stats` run of its own).  Needs a GPU."""
 import argparse
 import ctypes
@@ -21,7 +23,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from ken_burns_effect_amd import _native, gif, pipeline  # noqa: E402
+from ken_burns_effect_amd import _native, area, gif, pipeline  # noqa: E402
 
 
 def photo_like(n, size, device):
@@ -34,6 +36,62 @@ def photo_like(n, size, device):
         img[size // 4:size // 2, size // 3 + i:2 * size // 3 + i] = torch.tensor([220.0, 40.0, 60.0], device=device)
         frames[i] = (img + 4 * torch.randn(img.shape, generator=g, device=device)).clamp(0, 255).to(torch.uint8)
     return frames
+
+
+def gif_reduced_main(args):
+    """--format gif --gif-width N / --gif-every K: what gif.write_gif does short of the file, at the frames' own size and every frame against
+    size=(N, its height), every=K; milliseconds per clip, the bytes of the file (forth and back), and area.reduce alone by HIP events."""
+    lines = []
+    for spec in args.sizes.split(','):
+        size, n = (int(v) for v in spec.split('x'))
+        frames = photo_like(n, size, torch.device('cuda'))
+        w, h = area.size_for(size, size, width=args.gif_width)
+        kept = gif.kept_frames(n, args.gif_every)
+        index = torch.tensor(kept, device=frames.device)
+
+        def route(reduced):
+            chosen = frames
+            if reduced:
+                chosen = frames.index_select(0, index) if args.gif_every != 1 else frames
+                chosen = area.reduce(chosen, w, h) if (w, h) != (size, size) else chosen
+            palette = gif.palette_from_histogram(gif.histogram(chosen))
+            units = gif.encode(chosen, gif.lut(palette), dither='ordered', delay_cs=gif.delay_for(25.0 / (args.gif_every if reduced else 1)))
+            return gif.assemble(units + units[-2::-1], int(chosen.shape[2]), int(chosen.shape[1]), palette)
+
+        files = {'full': route(False), 'reduced': route(True)}           # warm-up, and the bytes to look at
+        if args.profile:
+            for _ in range(args.rounds):
+                route(True)
+            torch.cuda.synchronize()
+            continue
+        times = {'full': [], 'reduced': []}
+        while any(sum(t) < args.seconds or len(t) < 3 for t in times.values()):          # taking turns
+            for name in times:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                route(name == 'reduced')
+                torch.cuda.synchronize()
+                times[name].append(time.perf_counter() - t0)
+        chosen = frames.index_select(0, index)
+        reduce_ms = []
+        for _ in range(9):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            area.reduce(chosen, w, h)
+            e1.record()
+            torch.cuda.synchronize()
+            reduce_ms.append(e0.elapsed_time(e1))
+        line = dict(what='frames in HBM -> an animated GIF on the host, at their own size and reduced', size=size, frames=n, gpu=torch.cuda.get_device_name(0),
+                    gif_size=[w, h], gif_every=args.gif_every, frames_kept=len(kept),
+                    full_ms_per_clip=1e3 * float(np.median(times['full'])), reduced_ms_per_clip=1e3 * float(np.median(times['reduced'])),
+                    full_file_bytes=len(files['full']), reduced_file_bytes=len(files['reduced']), calls={name: len(t) for name, t in times.items()},
+                    area_reduce_ms_per_clip={'median': float(np.median(reduce_ms)), 'min': min(reduce_ms), 'with_its_allocation': True})
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if args.out and lines:
+        with open(args.out, 'w') as f:
+            for line in lines:
+                f.write(json.dumps(line) + '\n')
 
 
 def gif_main(args):
@@ -135,6 +193,8 @@ def main():
     ap.add_argument('--seconds', type=float, default=3.0)
     ap.add_argument('--quality', type=int, default=92, help='mjpeg')
     ap.add_argument('--threads', type=int, default=16, help='host threads of the host arm')
+    ap.add_argument('--gif-width', type=int, default=None, help='gif: also the route at this width (reduced on the GPU), against the full size')
+    ap.add_argument('--gif-every', type=int, default=1, help='gif: ... and keeping every so-many-th frame and the last')
     ap.add_argument('--out', default=None)
     ap.add_argument('--profile', action='store_true')
     ap.add_argument('--rounds', type=int, default=5)
@@ -145,7 +205,7 @@ def main():
     assert not mjpeg or pipeline.jpeg_encoder()[0] == 'native'
     own = (args.quality, 0) if mjpeg else (0,)                      # the entry's integers between the stride and the scratch
     if args.format == 'gif':
-        return gif_main(args)
+        return gif_reduced_main(args) if args.gif_width is not None or args.gif_every != 1 else gif_main(args)
     pipeline.WRITER_THREADS = args.threads
     os.environ.pop('KBE_WRITER_THREADS', None)
     lines = []
