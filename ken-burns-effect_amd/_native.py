@@ -17,6 +17,7 @@ import os
 import torch
 
 from . import _cabi, video_shape
+from ._cabi import KbeError
 # (the flag bits under the header's names, and the rules and thresholds of a video call's shape that lived here before video_shape.py did)
 from .video_shape import (DEFAULT_FILL_GROUP, DEFAULT_HOST_LANES, FUSED_DENSE, FUSED_HOST_GROUP, KBE_STAGE_FUSED_LEAN, KBE_STAGE_FUSED_ROOMY,  # noqa: F401
                           KBE_STAGE_PROJECT, KBE_VIDEO_FILL_DIST, KBE_VIDEO_FILL_GROUP, KBE_VIDEO_GROUP, KBE_VIDEO_FREE_TRANSFERS,
@@ -84,22 +85,8 @@ def host_lanes(lanes, n_points, W, H, frame_bytes):
 
 
 _lib = None
-_protos = None
-
-
-class KbeError(RuntimeError):
-    pass
-
-
-def prototypes():
-    """{entry: (restype, [argtypes])} of every entry include/kbe.h declares, in its order (_cabi.prototypes), read once."""
-    global _protos
-    if _protos is None:
-        if not os.path.exists(HEADER_PATH):
-            raise KbeError('%s is missing: the binding takes the types of every entry of libkbe_hip.so from it' % HEADER_PATH)
-        with open(HEADER_PATH) as f:
-            _protos = _cabi.prototypes(f.read(), 'KBE_API')
-    return _protos
+HEADER = _cabi.Header(HEADER_PATH, 'KBE_API', 'include/kbe.h', abi=('kbe_abi_version', ABI_VERSION, ''))
+prototypes = HEADER.prototypes     # {entry: (restype, [argtypes])} of every entry include/kbe.h declares, in its order, read once
 
 
 def __getattr__(name):
@@ -116,16 +103,8 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise KbeError('HIP extension not built: %s is missing. Run `python -c "import __graft_entry__ as g; g.build()"` '
                        '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
-    protos = prototypes()
-    lib = ctypes.CDLL(LIB_PATH)
-    for name in protos:
-        if not hasattr(lib, name):
-            raise KbeError('libkbe_hip.so does not export %s (stale build?)' % name)
-    _cabi.bind(lib, protos)
-    if lib.kbe_abi_version() != ABI_VERSION:
-        raise KbeError('libkbe_hip.so ABI %d != expected %d' % (lib.kbe_abi_version(), ABI_VERSION))
-    _lib = lib
-    return lib
+    _lib = HEADER.bind(ctypes.CDLL(LIB_PATH))
+    return _lib
 
 
 def _ptr(t, dtype=torch.float32):
@@ -175,6 +154,40 @@ def _group_args(cameras, scratch, stride, out=None, fill_rect=None):
     sets = (ctypes.c_void_p * n)(*[scratch.data_ptr() + k * stride for k in range(n)])
     frames = None if out is None else (ctypes.c_void_p * n)(*[out[k].data_ptr() for k in range(n)])
     return focals, shifts, sets, frames, _rect(fill_rect)
+
+
+def frame_pointers(frames, what):
+    """A uint8 [n,H,W,3] tensor of frames on the GPU -> (n, H, W, the bytes of a frame, the array of the frames' addresses); `what`: the caller, for the refusal."""
+    if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.size(3) == 3 and frames.size(0) >= 1):
+        raise KbeError('%s takes a uint8 [n,H,W,3] tensor on the GPU' % what)
+    n, H, W, _ = frames.shape
+    base, step = _ptr(frames, torch.uint8).value, H * W * 3
+    return n, H, W, step, (ctypes.c_void_p * n)(*[base + i * step for i in range(n)])
+
+
+def encode_units(what, name, frames, scratch_bytes, cap, first_guess, entry):
+    """The whole of a tensor-level call of a unit encoder (the encoders' common contract, include/kbe.h; gif.py's entry keeps it too) -> the
+    bytes of each frame's unit.  what, name: the caller and its entry, for messages; scratch_bytes: the entry's kbe_<fmt>_scratch_bytes;
+    first_guess(n, the bytes of a frame): the buffer's size when `cap` is None; entry(frames, n, W, H, stride, scratch, out, cap, offsets,
+    status, stream): the one call, which puts its own arguments where its header has them and raises unless KBE_OK.  One synchronisation
+    for the offsets and the status word; units that do not fit are encoded once more into a buffer of the size the first run reported."""
+    n, H, W, step, pointers = frame_pointers(frames, what)
+    device = frames.device
+    scratch = torch.empty((int(scratch_bytes(W, H, n)) + 7) // 8 + 1, dtype=torch.int64, device=device)
+    meta = torch.empty(n + 2, dtype=torch.int64, device=device)          # offsets [n + 1], then the status word
+    cap = int(cap) if cap is not None else first_guess(n, step)
+    for attempt in (0, 1):
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+        entry(pointers, n, W, H, 3 * W, scratch.data_ptr(), out.data_ptr(), cap, meta.data_ptr(), meta.data_ptr() + 8 * (n + 1), _stream())
+        host = meta.cpu()                                               # (the one synchronisation)
+        offsets, overflow = host[:n + 1].tolist(), int(host[n + 1].item()) & 0xFFFFFFFF
+        if not overflow:
+            break
+        if attempt == 1:
+            raise KbeError('%s: %d bytes do not fit a buffer of %d' % (name, offsets[n], cap))
+        cap = offsets[n]
+    data = out[:offsets[n]].cpu().numpy()
+    return [data[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
 
 
 _BUILD_BITS = {'lean': (KBE_STAGE_FUSED_LEAN, KBE_VIDEO_FUSED_LEAN), 'roomy': (KBE_STAGE_FUSED_ROOMY, KBE_VIDEO_FUSED_ROOMY)}
@@ -236,19 +249,12 @@ class HipKernels:
         self._tiled_scratch = {}      # (device, W, H) -> scratch of the tiled render_pointcloud
 
     def _check(self, rc, what):
-        if rc != 0:
-            raise KbeError('%s failed (%d): %s' % (what, rc, self.lib.kbe_last_error().decode()))
+        HEADER.check(self.lib, rc, what)
 
     def _raw(self, name, *args):
-        """The entry `name` of include/kbe.h with plain Python values -> what it returns.  ctypes holds the values to the header's types
-        (load); a surplus argument, which cdecl lets through, is refused here.  The entry is looked up on self.lib at each call (a tool
-        may have put a shim there)."""
-        proto = prototypes().get(name)
-        if proto is None:
-            raise KbeError('%s is not an entry of include/kbe.h' % name)
-        if len(args) != len(proto[1]):
-            raise KbeError('%s takes %d arguments, got %d' % (name, len(proto[1]), len(args)))
-        return getattr(self.lib, name)(*args)
+        """The entry `name` of include/kbe.h with plain Python values -> what it returns (_cabi.Header.raw: held to the header's types and
+        argument count, looked up on self.lib at each call -- a tool may have put a shim there)."""
+        return HEADER.raw(self.lib, name, *args)
 
     def _call(self, name, *args, what=None):
         """An entry that returns a status: KbeError with the library's text (under the label `what`, default the entry's name) unless KBE_OK."""
@@ -716,37 +722,16 @@ class HipKernels:
         entry's integers between the stride and the scratch (the quality, the flags).  -> its return code."""
         return self._raw('kbe_%s_encode' % fmt, pointers, n, W, H, stride, *own, scratch, out, cap, offsets, status, _stream())
 
-    def _encode(self, fmt, frames, own, cap, first_guess):
-        """The whole of a tensor-level call of kbe_<fmt>_encode: -> the bytes of each frame."""
-        if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.size(3) == 3 and frames.size(0) >= 1):
-            raise KbeError('%s_encode takes a uint8 [n,H,W,3] tensor on the GPU' % fmt)
-        n, H, W, _ = frames.shape
-        base, step = _ptr(frames, torch.uint8).value, H * W * 3
-        pointers = (ctypes.c_void_p * n)(*[base + i * step for i in range(n)])
-        device = frames.device
-        scratch = torch.empty((int(getattr(self.lib, 'kbe_%s_scratch_bytes' % fmt)(W, H, n)) + 7) // 8 + 1, dtype=torch.int64, device=device)
-        meta = torch.empty(n + 2, dtype=torch.int64, device=device)          # offsets [n + 1], then the status word
-        cap = int(cap) if cap is not None else first_guess(n, step)
-        for attempt in (0, 1):
-            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
-            self._check(self.encode_raw(fmt, pointers, n, W, H, 3 * W, own, scratch.data_ptr(), out.data_ptr(), cap, meta.data_ptr(), meta.data_ptr() + 8 * (n + 1)), 'kbe_%s_encode' % fmt)
-            host = meta.cpu()                                               # (the one synchronisation)
-            offsets, overflow = host[:n + 1].tolist(), int(host[n + 1].item()) & 0xFFFFFFFF
-            if not overflow:
-                break
-            if attempt == 1:
-                raise KbeError('kbe_%s_encode: %d bytes do not fit a buffer of %d' % (fmt, offsets[n], cap))
-            cap = offsets[n]
-        data = out[:offsets[n]].cpu().numpy()
-        return [data[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
-
     def mjpeg_encode(self, frames, quality=92, bgr=False, cap=None):
         """uint8 [n,H,W,3] frames in HBM -> one baseline JPEG (bytes) per frame, encoded on the device (kbe_mjpeg_encode): the streams
         come to the host, not the pixels.  ``bgr``: the frames hold B, G, R (what Pipeline renders from a cv2.imread image).  One
         synchronisation for the offsets and the status word, then exactly offsets[n] bytes are copied.  ``cap``: the stream buffer's
         size (default: a quarter of the raw frames -- photographs at quality 92 take about a tenth); when the streams do not fit,
         the call is repeated once with a buffer of the true size, which the first run has reported."""
-        return self._encode('mjpeg', frames, (int(quality), KBE_MJPEG_BGR if bgr else 0), cap, lambda n, step: n * (1024 + step // 4))
+        quality, flags = int(quality), KBE_MJPEG_BGR if bgr else 0
+        return encode_units('mjpeg_encode', 'kbe_mjpeg_encode', frames, self.lib.kbe_mjpeg_scratch_bytes, cap, lambda n, step: n * (1024 + step // 4),
+                            lambda pointers, n, W, H, stride, scratch, out, cap, offsets, status, stream:
+                            self._call('kbe_mjpeg_encode', pointers, n, W, H, stride, quality, flags, scratch, out, cap, offsets, status, stream))
 
     def png_encode(self, frames, bgr=False, cap=None):
         """uint8 [n,H,W,3] frames in HBM -> one PNG file (bytes) per frame, encoded on the device (kbe_png_encode): lossless, a file decodes
@@ -754,7 +739,10 @@ class HipKernels:
         One synchronisation for the offsets and the status word, then exactly offsets[n] bytes are copied.  ``cap``: the files' buffer
         (default: the raw size of the frames plus a kilobyte per frame -- only noise needs more); when the files do not fit, the call is
         repeated once with a buffer of the true size, which the first run has reported."""
-        return self._encode('png', frames, (KBE_PNG_BGR if bgr else 0,), cap, lambda n, step: n * (1024 + step))
+        flags = KBE_PNG_BGR if bgr else 0
+        return encode_units('png_encode', 'kbe_png_encode', frames, self.lib.kbe_png_scratch_bytes, cap, lambda n, step: n * (1024 + step),
+                            lambda pointers, n, W, H, stride, scratch, out, cap, offsets, status, stream:
+                            self._call('kbe_png_encode', pointers, n, W, H, stride, flags, scratch, out, cap, offsets, status, stream))
 
     # -- torch glue ---------------------------------------------------------------------
     def depth_to_points(self, depth, focal, valid=None):

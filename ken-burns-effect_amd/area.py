@@ -7,9 +7,9 @@ becomes (2 S + W H) // (2 W H), the mean rounded half up.  The same size copies.
 filter rounds between its two passes and differs by a count here and there (tests/test_area_stream.py).
 
 This is the only module that names the entries of kbe_area.h: they are exported by libkbe_hip.so beside those of kbe.h and kbe_gif.h and typed
-from their own header, the way gif.py types its own.  No fallback: without the HIP library every call here raises.
+from their own header on the package's one handle of that library, the way gif.py types its own.  No fallback: without the HIP library every
+call here raises.
 """
-import ctypes
 import os
 
 from . import _cabi, _native
@@ -17,52 +17,23 @@ from . import _cabi, _native
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'kbe_area.h')
 ABI_VERSION = 1
 MAX_SIDE = 65535
-_lib = None
-_protos = None
-
-
-def prototypes():
-    """{entry: (restype, [argtypes])} of every entry include/kbe_area.h declares, in its order, read once."""
-    global _protos
-    if _protos is None:
-        if not os.path.exists(HEADER_PATH):
-            raise _native.KbeError('%s is missing: the binding takes the types of the area entries of libkbe_hip.so from it' % HEADER_PATH)
-        with open(HEADER_PATH) as f:
-            _protos = _cabi.prototypes(f.read(), 'KBE_AREA_API')
-    return _protos
+HEADER = _cabi.Header(HEADER_PATH, 'KBE_AREA_API', 'include/kbe_area.h', abi=('kbe_area_abi_version', ABI_VERSION, 'area '))
+prototypes = HEADER.prototypes     # {entry: (restype, [argtypes])} of every entry include/kbe_area.h declares, in its order, read once
 
 
 def load():
-    """libkbe_hip.so once more, through a handle of this module's own, its area entries typed from include/kbe_area.h."""
-    global _lib
-    if _lib is None:
-        _native.load()                                                     # (says what to do when the library has not been built)
-        lib = ctypes.CDLL(_native.LIB_PATH)
-        for name in prototypes():
-            if not hasattr(lib, name):
-                raise _native.KbeError('libkbe_hip.so does not export %s (stale build?)' % name)
-        _cabi.bind(lib, prototypes())
-        if lib.kbe_area_abi_version() != ABI_VERSION:
-            raise _native.KbeError('libkbe_hip.so area ABI %d != expected %d' % (lib.kbe_area_abi_version(), ABI_VERSION))
-        _lib = lib
-    return _lib
+    """The package's one handle of libkbe_hip.so (_native.load), its area entries typed from include/kbe_area.h the first time it is seen."""
+    return HEADER.bind(_native.load())
 
 
 def _raw(name, *args):
-    """The entry `name` of include/kbe_area.h with plain Python values -> what it returns; a surplus argument, which cdecl lets through, is refused here."""
-    proto = prototypes().get(name)
-    if proto is None:
-        raise _native.KbeError('%s is not an entry of include/kbe_area.h' % name)
-    if len(args) != len(proto[1]):
-        raise _native.KbeError('%s takes %d arguments, got %d' % (name, len(proto[1]), len(args)))
-    return getattr(load(), name)(*args)
+    """The entry `name` of include/kbe_area.h with plain Python values -> what it returns; a surplus argument, which cdecl lets through, is refused."""
+    return HEADER.raw(load(), name, *args)
 
 
 def _call(name, *args):
     """An entry that returns a status: KbeError with the library's text unless KBE_OK."""
-    rc = _raw(name, *args)
-    if rc != 0:
-        raise _native.KbeError('%s failed (%d): %s' % (name, rc, _native.load().kbe_last_error().decode()))
+    HEADER.call(load(), name, *args)
 
 
 def size_for(W, H, width=None, height=None):
@@ -90,16 +61,11 @@ def reduce(frames_in_hbm, w, h):
     """uint8 [n,H,W,3] frames in HBM -> uint8 [n,h,w,3] on the same device, w <= W and h <= H: the exact area average (kbe_area_reduce_u8).
     Asynchronous on the current stream."""
     import torch
-    frames = frames_in_hbm
-    if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.size(3) == 3 and frames.size(0) >= 1):
-        raise _native.KbeError('area.reduce takes a uint8 [n,H,W,3] tensor on the GPU')
-    n, H, W, _ = frames.shape
+    n, H, W, _, sources = _native.frame_pointers(frames_in_hbm, 'area.reduce')
     w, h = int(w), int(h)
     if not (1 <= w <= W and 1 <= h <= H):
         raise _native.KbeError('area.reduce: %dx%d from %dx%d frames: the sides are 1..%d and 1..%d, frames are only reduced' % (w, h, W, H, W, H))
-    base = _native._ptr(frames, torch.uint8).value
-    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=frames.device)
-    sources = (ctypes.c_void_p * n)(*[base + i * H * W * 3 for i in range(n)])
-    targets = (ctypes.c_void_p * n)(*[out.data_ptr() + i * h * w * 3 for i in range(n)])
+    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=frames_in_hbm.device)
+    targets = _native.frame_pointers(out, 'area.reduce')[4]
     _call('kbe_area_reduce_u8', sources, n, W, H, 3 * W, targets, w, h, 3 * w, _native._stream())
     return out

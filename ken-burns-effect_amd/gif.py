@@ -3,13 +3,12 @@ is defined in csrc/kbe_gif_block.h).  Opt-in: ``Pipeline(gif=True)`` / env KBE_G
 
 The device writes one UNIT per frame (graphic control extension, image descriptor, LZW data); this module binds the entries, chooses the
 one global palette (a count-weighted median cut of the frames' RGB555 histogram, on the host: 32 768 counts) and assembles the file.  It is
-the only module that names the entries of kbe_gif.h: they are exported by libkbe_hip.so beside those of kbe.h, typed from their own header
-the way pipeline.jpeg_encoder types libkbe_jpeg.so.  No fallback: without the HIP library every call here raises.
+the only module that names the entries of kbe_gif.h: they are exported by libkbe_hip.so beside those of kbe.h and typed from their own header
+on the package's one handle of that library (_native.load; _cabi.Header).  No fallback: without the HIP library every call here raises.
 
 write_gif(size=, every=) writes a GIF smaller than the render and of fewer frames (``kbe.py --gif-width, --gif-fps``): the frames are reduced on
 the device first, by area.reduce (area.py binds that entry; this module names none of its).
 """
-import ctypes
 import os
 import struct
 from fractions import Fraction
@@ -23,67 +22,29 @@ ABI_VERSION = 1
 KBE_GIF_BGR = 1
 CELLS = 32768
 DITHER = {'none': 0, 'ordered': 8}      # the amplitude of the ordered dither: 8 is one step of a 5-bit channel
-_lib = None
-_protos = None
-
-
-def prototypes():
-    """{entry: (restype, [argtypes])} of every entry include/kbe_gif.h declares, in its order, read once."""
-    global _protos
-    if _protos is None:
-        if not os.path.exists(HEADER_PATH):
-            raise _native.KbeError('%s is missing: the binding takes the types of the GIF entries of libkbe_hip.so from it' % HEADER_PATH)
-        with open(HEADER_PATH) as f:
-            _protos = _cabi.prototypes(f.read(), 'KBE_GIF_API')
-    return _protos
+HEADER = _cabi.Header(HEADER_PATH, 'KBE_GIF_API', 'include/kbe_gif.h', abi=('kbe_gif_abi_version', ABI_VERSION, 'GIF '))
+prototypes = HEADER.prototypes     # {entry: (restype, [argtypes])} of every entry include/kbe_gif.h declares, in its order, read once
 
 
 def load():
-    """libkbe_hip.so once more, through a handle of this module's own, its GIF entries typed from include/kbe_gif.h."""
-    global _lib
-    if _lib is None:
-        _native.load()                                                     # (says what to do when the library has not been built)
-        lib = ctypes.CDLL(_native.LIB_PATH)
-        for name in prototypes():
-            if not hasattr(lib, name):
-                raise _native.KbeError('libkbe_hip.so does not export %s (stale build?)' % name)
-        _cabi.bind(lib, prototypes())
-        if lib.kbe_gif_abi_version() != ABI_VERSION:
-            raise _native.KbeError('libkbe_hip.so GIF ABI %d != expected %d' % (lib.kbe_gif_abi_version(), ABI_VERSION))
-        _lib = lib
-    return _lib
+    """The package's one handle of libkbe_hip.so (_native.load), its GIF entries typed from include/kbe_gif.h the first time it is seen."""
+    return HEADER.bind(_native.load())
 
 
 def _raw(name, *args):
-    """The entry `name` of include/kbe_gif.h with plain Python values -> what it returns; a surplus argument, which cdecl lets through, is refused here."""
-    proto = prototypes().get(name)
-    if proto is None:
-        raise _native.KbeError('%s is not an entry of include/kbe_gif.h' % name)
-    if len(args) != len(proto[1]):
-        raise _native.KbeError('%s takes %d arguments, got %d' % (name, len(proto[1]), len(args)))
-    return getattr(load(), name)(*args)
+    """The entry `name` of include/kbe_gif.h with plain Python values -> what it returns; a surplus argument, which cdecl lets through, is refused."""
+    return HEADER.raw(load(), name, *args)
 
 
 def _call(name, *args):
     """An entry that returns a status: KbeError with the library's text unless KBE_OK."""
-    rc = _raw(name, *args)
-    if rc != 0:
-        raise _native.KbeError('%s failed (%d): %s' % (name, rc, _native.load().kbe_last_error().decode()))
-
-
-def _frames(frames, what):
-    import torch
-    if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.size(3) == 3 and frames.size(0) >= 1):
-        raise _native.KbeError('%s takes a uint8 [n,H,W,3] tensor on the GPU' % what)
-    n, H, W, _ = frames.shape
-    base, step = _native._ptr(frames, torch.uint8).value, H * W * 3
-    return n, H, W, step, (ctypes.c_void_p * n)(*[base + i * step for i in range(n)])
+    HEADER.call(load(), name, *args)
 
 
 def histogram(frames, bgr=False):
     """uint8 [n,H,W,3] frames in HBM -> the number of their pixels in each RGB555 cell (r5 << 10 | g5 << 5 | b5), NumPy int64 [32768]."""
     import torch
-    n, H, W, _, pointers = _frames(frames, 'gif.histogram')
+    n, H, W, _, pointers = _native.frame_pointers(frames, 'gif.histogram')
     hist = torch.zeros(CELLS, dtype=torch.int32, device=frames.device)
     _call('kbe_gif_histogram', pointers, n, W, H, 3 * W, KBE_GIF_BGR if bgr else 0, hist.data_ptr(), _native._stream())
     return hist.cpu().numpy().view(np.uint32).astype(np.int64)
@@ -166,27 +127,13 @@ def encode(frames, lut, bgr=False, dither='ordered', delay_cs=4, cap=None):
     the status word, then exactly offsets[n] bytes are copied.  ``cap``: the buffer's size (default: 0.6 bytes per pixel -- noisy photographs take 0.5 -- and a kilobyte per
     frame); when the units do not fit, the call is repeated once with a buffer of the true size, which the first run has reported."""
     import torch
-    n, H, W, step, pointers = _frames(frames, 'gif.encode')
-    device = frames.device
     table = _native._ptr(lut, torch.uint8)
     if lut.numel() != CELLS:
         raise _native.KbeError('gif.encode takes a lut of %d bytes' % CELLS)
-    scratch = torch.empty((int(load().kbe_gif_scratch_bytes(W, H, n)) + 7) // 8 + 1, dtype=torch.int64, device=device)
-    meta = torch.empty(n + 2, dtype=torch.int64, device=device)          # offsets [n + 1], then the status word
-    cap = int(cap) if cap is not None else n * (1024 + step // 5)
-    for attempt in (0, 1):
-        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
-        _call('kbe_gif_encode', pointers, n, W, H, 3 * W, KBE_GIF_BGR if bgr else 0, _amplitude(dither), int(delay_cs), table, scratch.data_ptr(), out.data_ptr(), cap,
-              meta.data_ptr(), meta.data_ptr() + 8 * (n + 1), _native._stream())
-        host = meta.cpu()                                               # (the one synchronisation)
-        offsets, overflow = host[:n + 1].tolist(), int(host[n + 1].item()) & 0xFFFFFFFF
-        if not overflow:
-            break
-        if attempt == 1:
-            raise _native.KbeError('kbe_gif_encode: %d bytes do not fit a buffer of %d' % (offsets[n], cap))
-        cap = offsets[n]
-    data = out[:offsets[n]].cpu().numpy()
-    return [data[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
+    flags, amplitude, delay_cs = KBE_GIF_BGR if bgr else 0, _amplitude(dither), int(delay_cs)
+    return _native.encode_units('gif.encode', 'kbe_gif_encode', frames, load().kbe_gif_scratch_bytes, cap, lambda n, step: n * (1024 + step // 5),
+                                lambda pointers, n, W, H, stride, scratch, out, cap, offsets, status, stream:
+                                _call('kbe_gif_encode', pointers, n, W, H, stride, flags, amplitude, delay_cs, table, scratch, out, cap, offsets, status, stream))
 
 
 def assemble(units, W, H, palette, loop=0):

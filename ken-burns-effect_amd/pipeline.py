@@ -228,8 +228,7 @@ def jpeg_encoder():
             warnings.warn('%s is missing (python -c "import __graft_entry__ as g; g.build()"): the video writer encodes with Pillow, one frame at a time' % _JPEG_LIB_PATH)
             return 'pillow', None
         from . import _cabi
-        with open(_JPEG_HEADER_PATH) as f:
-            _jpeg_lib = _cabi.bind(ctypes.CDLL(_JPEG_LIB_PATH), _cabi.prototypes(f.read(), 'KBE_JPEG_API'))
+        _jpeg_lib = _cabi.Header(_JPEG_HEADER_PATH, 'KBE_JPEG_API', 'include/kbe_jpeg.h', library='libkbe_jpeg.so').bind(ctypes.CDLL(_JPEG_LIB_PATH))
     return 'native', _jpeg_lib
 
 

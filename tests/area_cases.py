@@ -1,17 +1,16 @@
-"""What tests/test_area_stream.py, tests/test_area_binding.py (CPU) and tests/test_area_gpu.py share: the NumPy twin of the exact area-average
+"""What tests/test_area_stream.py, tests/test_header_bindings.py (CPU) and tests/test_area_gpu.py share: the NumPy twin of the exact area-average
 reduction (include/kbe_area.h; defined in csrc/kbe_area_block.h), the serial execution of that header (tests/area_check.cpp compiled by g++)
 and the frames of the cases."""
 import functools
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 
 import gif_cases as gc
+import twins
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_dir = None
 
 
 # -- the NumPy twin -------------------------------------------------------------------------
@@ -38,12 +37,7 @@ def twin_reduce(frames, w, h):
 # -- the header, serially -------------------------------------------------------------------
 def checker():
     """tests/area_check.cpp, built once per process: no -ffast-math, no -march."""
-    global _dir
-    if _dir is None:
-        _dir = tempfile.TemporaryDirectory(prefix='area_check')
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-I', os.path.join(ROOT, 'ken-burns-effect_amd', 'csrc'), os.path.join(ROOT, 'tests', 'area_check.cpp'),
-                               '-o', os.path.join(_dir.name, 'area_check')])
-    return os.path.join(_dir.name, 'area_check')
+    return twins.built('area_check')
 
 
 def ask(*args):
@@ -58,8 +52,7 @@ def header_reduce(frames, w, h, pad=0):
     n, H, W, _ = frames.shape
     rows = np.full((n, H, 3 * W + pad), 0xEE, np.uint8)
     rows[:, :, :3 * W] = frames.reshape(n, H, 3 * W)
-    checker()
-    src, dst = os.path.join(_dir.name, 'in.raw'), os.path.join(_dir.name, 'out.raw')
+    src, dst = (os.path.join(os.path.dirname(checker()), name) for name in ('in.raw', 'out.raw'))
     rows.tofile(src)
     ask('reduce', W, H, 3 * W + pad, w, h, n, src, dst)
     return np.fromfile(dst, np.uint8).reshape(n, h, w, 3)

@@ -1,4 +1,4 @@
-"""What tests/test_gif_stream.py, tests/test_gif_binding.py (CPU) and tests/test_gif_gpu.py share: the CPU twin of the device-side GIF encoder
+"""What tests/test_gif_stream.py, tests/test_header_bindings.py (CPU) and tests/test_gif_gpu.py share: the CPU twin of the device-side GIF encoder
 (tests/gif_check.cpp: csrc/kbe_gif_block.h compiled by g++), the cases and their frames, a NumPy restatement of pixel -> index, of the
 look-up table and of the histogram, and a small reader of GIF files that returns what Pillow does not show: the sub-blocks' sizes and the
 LZW codes with their widths and bit positions."""
@@ -7,10 +7,10 @@ import os
 import re
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
 
+import twins
 from test_jpeg_writer import photo_like
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,17 +18,11 @@ BGR = 1                                                     # include/kbe_gif.h:
 SEGMENT = 3838                                              # csrc/kbe_gif_block.h: kSegmentPixels (the twin prints it; test_gif_stream.py compares)
 DITHER = 8                                                  # gif.DITHER['ordered']
 CELLS = 32768
-_dir = None
 
 
 def checker():
     """The twin, built once per process: no -ffast-math, no -march."""
-    global _dir
-    if _dir is None:
-        _dir = tempfile.TemporaryDirectory(prefix='gif_check')
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-I', os.path.join(ROOT, 'ken-burns-effect_amd', 'csrc'), os.path.join(ROOT, 'tests', 'gif_check.cpp'),
-                               '-o', os.path.join(_dir.name, 'gif_check')])
-    return os.path.join(_dir.name, 'gif_check')
+    return twins.built('gif_check')
 
 
 def ask(*args):
@@ -42,8 +36,7 @@ def twin(frames, lut, flags=0, dither=0, delay_cs=4, pieces=False):
     in the kernels' steps."""
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, h, w, _ = frames.shape
-    checker()
-    src, table, dst = (os.path.join(_dir.name, name) for name in ('in.raw', 'lut.bin', 'out.bin'))
+    src, table, dst = (os.path.join(os.path.dirname(checker()), name) for name in ('in.raw', 'lut.bin', 'out.bin'))
     frames.tofile(src)
     np.ascontiguousarray(lut, dtype=np.uint8).reshape(CELLS).tofile(table)
     text = ask('encode_pieces' if pieces else 'encode', w, h, flags, dither, delay_cs, n, src, table, dst)

@@ -5,27 +5,21 @@ import os
 import re
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
 
+import twins
 from test_jpeg_writer import photo_like
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BGR = 1                                                     # include/kbe.h: KBE_MJPEG_BGR
 SIZES = [(96, 128), (50, 37), (17, 16), (16, 17), (1, 1), (3, 200)]
 QUALITIES = [10, 50, 75, 92, 100]
-_dir = None
 
 
 def checker():
     """The twin, built once per process with the flags that define the stream: no contraction, no -ffast-math, no -march."""
-    global _dir
-    if _dir is None:
-        _dir = tempfile.TemporaryDirectory(prefix='mjpeg_check')
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(ROOT, 'ken-burns-effect_amd', 'csrc'),
-                               os.path.join(ROOT, 'tests', 'mjpeg_check.cpp'), '-o', os.path.join(_dir.name, 'mjpeg_check')])
-    return os.path.join(_dir.name, 'mjpeg_check')
+    return twins.built('mjpeg_check', '-ffp-contract=off')
 
 
 def twin(frames, quality, flags=0, packed=False):
@@ -33,7 +27,7 @@ def twin(frames, quality, flags=0, packed=False):
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, h, w, _ = frames.shape
     exe = checker()
-    src, dst = os.path.join(_dir.name, 'in.raw'), os.path.join(_dir.name, 'out.bin')
+    src, dst = os.path.join(os.path.dirname(exe), 'in.raw'), os.path.join(os.path.dirname(exe), 'out.bin')
     frames.tofile(src)
     out = subprocess.run([exe, 'encode_packed' if packed else 'encode', str(w), str(h), str(quality), str(flags), str(n), src, dst], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-1000:]

@@ -5,28 +5,22 @@ import os
 import re
 import struct
 import subprocess
-import tempfile
 import zlib
 
 import numpy as np
 
+import twins
 from test_jpeg_writer import photo_like
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BGR = 1                                                     # include/kbe.h: KBE_PNG_BGR
 SEGMENT = 16384                                             # csrc/kbe_png_block.h: kSegmentBytes (the twin prints it; test_png_stream.py compares)
 SIZES = [(1, 1), (3, 200), (17, 16), (50, 37), (96, 128)]
-_dir = None
 
 
 def checker():
     """The twin, built once per process: no -ffast-math, no -march."""
-    global _dir
-    if _dir is None:
-        _dir = tempfile.TemporaryDirectory(prefix='png_check')
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-I', os.path.join(ROOT, 'ken-burns-effect_amd', 'csrc'), os.path.join(ROOT, 'tests', 'png_check.cpp'),
-                               '-o', os.path.join(_dir.name, 'png_check')])
-    return os.path.join(_dir.name, 'png_check')
+    return twins.built('png_check')
 
 
 def twin(frames, flags=0, pieces=False):
@@ -34,7 +28,7 @@ def twin(frames, flags=0, pieces=False):
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, h, w, _ = frames.shape
     exe = checker()
-    src, dst = os.path.join(_dir.name, 'in.raw'), os.path.join(_dir.name, 'out.bin')
+    src, dst = os.path.join(os.path.dirname(exe), 'in.raw'), os.path.join(os.path.dirname(exe), 'out.bin')
     frames.tofile(src)
     out = subprocess.run([exe, 'encode_pieces' if pieces else 'encode', str(w), str(h), str(flags), str(n), src, dst], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-1000:]

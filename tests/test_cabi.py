@@ -131,8 +131,9 @@ def test_call_reports_a_refusal_with_the_librarys_text():
 def test_load_names_a_missing_header(monkeypatch, tmp_path):
     from ken_burns_effect_amd import _native
     missing = str(tmp_path / 'include' / 'kbe.h')
-    monkeypatch.setattr(_native, 'HEADER_PATH', missing)
-    monkeypatch.setattr(_native, '_protos', None)
+    monkeypatch.setattr(_native.HEADER, 'path', missing)
+    monkeypatch.setattr(_native.HEADER, '_protos', None)
+    monkeypatch.setattr(_native.HEADER, '_bound', None)
     monkeypatch.setattr(_native, '_lib', None)
     with pytest.raises(_native.KbeError, match=missing):
         _native.load()

@@ -10,96 +10,59 @@ from PIL import Image
 
 import encoder_gpu as eg
 import gif_cases as gc
-import gif_gpu as gg
-from guarded import SENTINEL, Guard
+from guarded import Guard
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope='module')
-def G():
-    return gg.gif()
+def K():
+    return eg.kernels()
 
 
 @pytest.fixture(scope='module')
-def rendered():
-    return eg.rendered(eg.kernels())
+def G():
+    return eg.gif()
+
+
+@pytest.fixture(scope='module')
+def rendered(K):
+    return eg.rendered(K)
 
 
 @pytest.mark.parametrize('name', sorted(gc.CASES))
-def test_device_units_are_the_twins_byte_for_byte(G, name):
-    gg.assert_case(name)
+def test_device_units_are_the_twins_byte_for_byte(K, name):
+    eg.assert_case(K, eg.GIF, name, dithers=((0,), (gc.DITHER,)))
 
 
-def test_rows_apart_by_a_stride_wider_than_the_frame(G):
-    """W < the tensor's width: the entry reads the first 150 pixels of rows 160 pixels apart."""
+def test_rows_apart_by_a_stride_wider_than_the_frame(K):
+    """W < the tensor's width: the entry reads the first 150 pixels of rows 160 pixels apart, in both channel orders, the dither off and on."""
     frames = gc.case_frames('photo_like', 3)
     lut = gc.case_palette('photo_like')[1]
     for flags, dither in ((0, 0), (gc.BGR, gc.DITHER)):
         want = gc.twin(frames[:, :, :150], lut, flags, dither)[0]
-        gg.assert_units(frames, gg.on_device(lut), want, W=150, flags=flags, dither=dither)
+        eg.assert_units(K, eg.GIF, frames, (flags, dither, 4, eg.gif_lut('photo_like').data_ptr()), want, W=150)
 
 
-def test_an_unaligned_buffer_without_room(G):
+def test_an_unaligned_buffer_without_room(K):
     for name in ('noise', 'photo_like'):
-        lut = gg.on_device(gc.case_palette(name, gc.BGR)[1])
-        gg.assert_units(gc.case_frames(name, 3), lut, gc.case_twin(name, 3, gc.BGR, gc.DITHER)[0], room=0, shift=3, flags=gc.BGR, dither=gc.DITHER)
+        eg.assert_units(K, eg.GIF, gc.case_frames(name, 3), eg.GIF.own(name, gc.BGR, gc.DITHER), gc.case_twin(name, 3, gc.BGR, gc.DITHER)[0], room=0, shift=3)
 
 
-def test_the_scan_over_more_segments_than_one_of_its_workgroups_takes(G):
+def test_the_scan_over_more_segments_than_one_of_its_workgroups_takes(K, G):
     frames = eg.tiled(1000, 1000, 11)[None]
     palette = G.palette_from_histogram(gc.hist_of(frames))
     lut = gc.lut_of(palette)
     want, _, segment, _ = gc.twin(frames, lut)
     assert -(-1000 * 1000 // segment) > 256
-    gg.assert_units(frames, gg.on_device(lut), want)
+    table = eg.on_device(lut)                                               # (held here: the entry takes its address)
+    eg.assert_units(K, eg.GIF, frames, (0, 0, 4, table.data_ptr()), want)
 
 
-def test_a_buffer_that_is_too_small(G):
-    """status 1, the true offsets, the twin's bytes below cap and nothing at or beyond it; the rerun at offsets[n] succeeds."""
-    frames, lut = gg.on_device(gc.case_frames('photo_like', 3)), gg.on_device(gc.case_palette('photo_like')[1])
-    want = gc.case_twin('photo_like', 3)[0]
-    sizes, whole = gg.sizes_of(want), b''.join(want)
-    for cap in (0, 1, sizes[1] - 1, sizes[2] - 1, sizes[3] - 1):
-        rc, offsets, status, buf, _ = gg.run(frames, lut, cap)
-        assert rc == 0 and status == 1 and offsets == sizes
-        assert buf[:cap].tobytes() == whole[:cap] and (buf[cap:] == SENTINEL).all()
-    rc, offsets, status, buf, _ = gg.run(frames, lut, offsets[3])
-    assert rc == 0 and status == 0 and buf[:sizes[3]].tobytes() == whole and (buf[sizes[3]:] == SENTINEL).all()
-    # out may be NULL when cap is 0
-    rc, offsets, status, _, _ = gg.run(frames, lut, 0, change=lambda a: a.update(out=None))
-    assert rc == 0 and status == 1 and offsets == sizes
-
-
-REFUSALS = {'null frames': lambda a: a.update(frames_u8=None),
-            'null frame 1': lambda a: a['frames_u8'].__setitem__(1, None),
-            'n = 0': lambda a: a.update(n_frames=0),
-            'W = 0': lambda a: a.update(W=0),
-            'H = 0': lambda a: a.update(H=0),
-            'W = 65536': lambda a: a.update(W=65536, stride_bytes=3 * 65536),
-            'H = 65536': lambda a: a.update(H=65536),
-            'stride < 3 W': lambda a: a.update(stride_bytes=3 * a['W'] - 1),
-            'unknown flag': lambda a: a.update(flags=2),
-            'misaligned scratch': lambda a: a.update(scratch=a['scratch'] + 4),
-            'null scratch': lambda a: a.update(scratch=None),
-            'misaligned offsets': lambda a: a.update(offsets=a['offsets'] + 4),
-            'null status': lambda a: a.update(status=None),
-            'null out with a cap': lambda a: a.update(out=None),
-            'null lut': lambda a: a.update(lut=None),
-            'delay -1': lambda a: a.update(delay_cs=-1),
-            'delay 65536': lambda a: a.update(delay_cs=65536),
-            'dither -1': lambda a: a.update(dither=-1),
-            'dither 65': lambda a: a.update(dither=65),
-            'a refused size': lambda a: a.update(W=65535, H=65535, stride_bytes=3 * 65535)}
-
-
-@pytest.mark.parametrize('what', sorted(REFUSALS))
-def test_refusals_leave_every_buffer_untouched(G, what):
-    from ken_burns_effect_amd import _native
-    frames, lut = gg.on_device(gc.case_frames('17x16', 3)), gg.on_device(gc.case_palette('17x16')[1])
-    rc, offsets, status, buf, scratch_untouched = gg.run(frames, lut, 4096, change=REFUSALS[what])
-    assert rc == -1 and _native.load().kbe_last_error().decode().startswith('kbe_gif_encode: ')
-    assert offsets == [-1] * 4 and status == 7 and (buf == SENTINEL).all() and scratch_untouched
+@pytest.mark.parametrize('what', eg.refusals_of(eg.GIF))
+def test_refusals_leave_every_buffer_untouched(K, what):
+    """The refusals of the shared contract (tests/encoder_gpu.py: REFUSALS) and the GIF's own, one id each."""
+    eg.assert_refused(K, eg.GIF, what)
 
 
 def test_the_bound_and_the_scratch(G):
@@ -115,17 +78,17 @@ def test_the_bound_and_the_scratch(G):
 @pytest.mark.parametrize('bgr', [False, True], ids=['rgb', 'bgr'])
 def test_the_histogram_is_numpys_bincount_of_the_cells(G, bgr):
     frames = gc.case_frames('photo_like', 13)
-    assert np.array_equal(G.histogram(gg.on_device(frames), bgr=bgr), gc.hist_of(frames, bgr))
+    assert np.array_equal(G.histogram(eg.on_device(frames), bgr=bgr), gc.hist_of(frames, bgr))
     # a padded stride, and two calls that accumulate, on a guarded histogram
-    dev = gg.on_device(frames)
+    dev = eg.on_device(frames)
     guard = Guard()
     hist = guard.full((gc.CELLS,), 0, torch.int32, 'cuda')
     for part in (dev[:5], dev[5:]):
-        rc = G._raw('kbe_gif_histogram', gg.pointers_of(part), part.shape[0], 150, 128, 3 * 160, gc.BGR if bgr else 0, hist.data_ptr(), gg.stream())
+        rc = G._raw('kbe_gif_histogram', eg.pointers_of(part), part.shape[0], 150, 128, 3 * 160, gc.BGR if bgr else 0, hist.data_ptr(), eg.stream())
         assert rc == 0
     guard.check()
     assert np.array_equal(hist.cpu().numpy().astype(np.int64), gc.hist_of(frames[:, :, :150], bgr))
-    assert G._raw('kbe_gif_histogram', gg.pointers_of(dev), 13, 161, 128, 3 * 160, 0, hist.data_ptr(), gg.stream()) == -1
+    assert G._raw('kbe_gif_histogram', eg.pointers_of(dev), 13, 161, 128, 3 * 160, 0, hist.data_ptr(), eg.stream()) == -1
 
 
 def test_the_lut_is_the_restatements(G):
@@ -133,10 +96,10 @@ def test_the_lut_is_the_restatements(G):
     for palette in (rng.integers(0, 256, (256, 3), dtype=np.uint8), np.array([(200, 10, 10), (10, 10, 200), (200, 10, 10)], np.uint8), np.array([(1, 2, 3)], np.uint8)):
         assert np.array_equal(G.lut(palette).cpu().numpy(), gc.lut_of(palette))
     guard = Guard()
-    table, pal = guard.empty((gc.CELLS,), torch.uint8, 'cuda'), gg.on_device(np.zeros((256, 3), np.uint8))
+    table, pal = guard.empty((gc.CELLS,), torch.uint8, 'cuda'), eg.on_device(np.zeros((256, 3), np.uint8))
     for n in (0, 257):
-        assert G._raw('kbe_gif_lut', pal.data_ptr(), n, table.data_ptr(), gg.stream()) == -1
-    assert G._raw('kbe_gif_lut', pal.data_ptr(), 256, table.data_ptr(), gg.stream()) == 0
+        assert G._raw('kbe_gif_lut', pal.data_ptr(), n, table.data_ptr(), eg.stream()) == -1
+    assert G._raw('kbe_gif_lut', pal.data_ptr(), 256, table.data_ptr(), eg.stream()) == 0
     guard.check()
     assert (table == 0).all()
 
@@ -166,29 +129,13 @@ def test_write_gif_on_the_rendered_scene(G, rendered, tmp_path):
         assert np.array_equal(frame, _expected(raw[i if i < n else 2 * n - 2 - i], palette, True, gc.DITHER)), i
 
 
-def _stub(P, output_frames):
-    class Stub(P.Pipeline):
-        def __init__(self):
-            self.output_frames, self.dolly, self.steps, self.objectCommon, self.moduleInpaint, self.device = output_frames, False, 2, {}, None, torch.device('cuda:0')
-
-        def estimate(self, tensorImage):
-            return self.objectCommon
-    return Stub()
-
-
 @pytest.mark.parametrize('pretrained_estim', [False, True], ids=['bgr', 'rgb'])
 def test_the_pipeline_writes_the_gif_under_the_switch_and_nothing_else_changes(G, rendered, pretrained_estim, monkeypatch, tmp_path):
     """Pipeline._run with KBE_GIF=1: the frame loop is asked to leave its frames on the device, 3d_kbe.gif holds forth and back, and every
     other file is byte for byte what a run without the switch writes: the video, and frames/%d.png under KBE_PNG native and device."""
     from ken_burns_effect_amd import pipeline as P
     in_hbm, raw = rendered
-    asked = {}
-
-    def kenburns(settings, oc, module, keep_on_device=False):
-        asked['keep_on_device'] = keep_on_device
-        return in_hbm if keep_on_device else [f for f in raw]
-    monkeypatch.setattr(P.common, 'process_kenburns', kenburns)
-    monkeypatch.setattr(P.shutil, 'which', lambda name: None)
+    Stub, asked = eg.pipeline_without_models(P, monkeypatch, in_hbm, raw)
     monkeypatch.delenv('KBE_GIF', raising=False)
     monkeypatch.delenv('KBE_GIF_DITHER', raising=False)
     image, zoom = torch.zeros(1, 3, 96, 128), {'objectFrom': {}, 'objectTo': {}}
@@ -200,11 +147,11 @@ def test_the_pipeline_writes_the_gif_under_the_switch_and_nothing_else_changes(G
         monkeypatch.setenv('KBE_PNG', png)
         monkeypatch.setenv('KBE_JPEG', jpeg)
         plain, with_gif = tmp_path / ('plain%d' % at), tmp_path / ('gif%d' % at)
-        _stub(P, output_frames)(image, zoom, str(plain), pretrained_estim=pretrained_estim)
+        Stub(output_frames)(image, zoom, str(plain), pretrained_estim=pretrained_estim)
         before = files_of(plain)
         assert '3d_kbe.mp4' in before and '3d_kbe.gif' not in before and (('frames/1.png' in before) == output_frames)
         monkeypatch.setenv('KBE_GIF', '1')
-        out = _stub(P, output_frames)(image, zoom, str(with_gif), pretrained_estim=pretrained_estim)
+        out = Stub(output_frames)(image, zoom, str(with_gif), pretrained_estim=pretrained_estim)
         monkeypatch.delenv('KBE_GIF')
         assert asked['keep_on_device'] is True
         assert len(out) == 2 and all(isinstance(f, np.ndarray) and np.array_equal(f, r) for f, r in zip(out, raw))

@@ -75,20 +75,7 @@ def test_the_pipeline_keeps_its_frames_in_hbm_under_the_switch(K, rendered, pret
     encoded once (in the input's channel order), the video goes forth and back, and the frames come back as numpy arrays all the same."""
     from ken_burns_effect_amd import pipeline as P
     in_hbm, raw = rendered
-    asked = {}
-
-    class Stub(P.Pipeline):
-        def __init__(self, output_frames):
-            self.output_frames, self.dolly, self.steps, self.objectCommon, self.moduleInpaint, self.device = output_frames, False, 2, {}, None, torch.device('cuda:0')
-
-        def estimate(self, tensorImage):
-            return self.objectCommon
-
-    def kenburns(settings, oc, module, keep_on_device=False):
-        asked['keep_on_device'] = keep_on_device
-        return in_hbm if keep_on_device else [f for f in raw]
-    monkeypatch.setattr(P.common, 'process_kenburns', kenburns)
-    monkeypatch.setattr(P.shutil, 'which', lambda name: None)
+    Stub, asked = eg.pipeline_without_models(P, monkeypatch, in_hbm, raw)
     monkeypatch.setenv('KBE_JPEG', 'device')
     image = torch.zeros(1, 3, 96, 128)
     out = Stub(False)(image, {'objectFrom': {}, 'objectTo': {}}, str(tmp_path), pretrained_estim=pretrained_estim)
