@@ -319,7 +319,7 @@ def _prepared_cloud(K, objectCommon):
     return cached[1]
 
 
-def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_out=None, overlap=True, batch=None):
+def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_out=None, overlap=True, batch=None, out_size=None):
     """The frame loop proper (common.py:238-257) for a list of (focal, shift3) cameras.
 
     One fused kernel sequence per frame on the resident packed cloud; frames land in one
@@ -327,7 +327,17 @@ def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_o
     device-side equivalent of cv2.getRectSubPix + cv2.resize (common.py:256-257); None
     returns the un-cropped frames.  Returns uint8 [n,H,W,3] (numpy, or a device tensor when
     ``keep_on_device``).  ``host_out``: optional pre-allocated uint8 [n,H,W,3] tensor to land the frames in
-    (pinned host memory, or device memory with ``keep_on_device``; otherwise a fresh one is allocated per call)."""
+    (pinned host memory, or device memory with ``keep_on_device``; otherwise a fresh one is allocated per call).
+
+    ``out_size`` = (w, h) with ``crop``: frames of that size instead of the photo's, w <= crop[0] and h <= crop[1] -- the crop's patch
+    reduced by the exact area average, one kernel that reads the raw frame (crop_area.reduce: patch, then area mean; not the enlargement to
+    W x H reduced again, which would resample twice).  The frames are rendered with crop=None into HBM, reduced there, and the reduced
+    frames are returned or fetched; host_out, overlap and batch do not apply.  What it costs: with crop=None the hole fill runs on the
+    whole frame and not only inside the crop's window, and the fetch does not overlap the rendering.  Why it is right: a hole outside
+    the window never sources a fill (deviation 7), so the pixels the patch reads are the ones the cropped route
+    would have produced."""
+    if out_size is not None:
+        return _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device)
     K = _K()
     W, H = objectCommon['intWidth'], objectCommon['intHeight']
     state = _prepared_cloud(K, objectCommon)
@@ -354,18 +364,35 @@ def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_o
     return out if keep_on_device else out.cpu().numpy()
 
 
-def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False):
+def _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device):
+    """render_frames(out_size=...): the raw frames in HBM, then their crop reduced there (crop_area.reduce)."""
+    from . import crop_area
+    if crop is None:
+        raise ValueError('render_frames(out_size=...) reduces the crop: it needs crop=(w, h)')
+    raw = render_frames(cameras, objectCommon, None, keep_on_device=True)
+    out = crop_area.reduce(raw, crop, out_size)
+    if keep_on_device:
+        return out
+    # (into pinned memory, as the frames of the photo's size land: a copy into pageable memory runs at a seventh of the link's rate)
+    host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return host.numpy()
+
+
+def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False, out_size=None):
     """Renders the camera path ``dblSteps`` between two crop windows (common.py:172-263).
 
     objectSettings: dblSteps, objectFrom/objectTo {dblCenterU, dblCenterV, intCropWidth,
     intCropHeight}, boolInpaint (default True), dolly.  Returns a list of uint8 HxWx3 frames.
     Optional key ``boolCrop`` (default True): apply the crop + resize of :256-257.  ``keep_on_device``: the frames stay in HBM and
-    come back as one uint8 [n,H,W,3] device tensor (for the device-side Motion-JPEG encoder)."""
+    come back as one uint8 [n,H,W,3] device tensor (for the device-side Motion-JPEG encoder).  ``out_size`` = (w, h): frames of that size,
+    the crop reduced on the GPU and never enlarged (render_frames(out_size=...)); it needs the crop (``boolCrop``)."""
     with on_device_of(objectCommon['tensorRawPoints']):
         if 'boolInpaint' not in objectSettings or objectSettings['boolInpaint'] == True:   # noqa: E712
             build_pointcloud(objectSettings, objectCommon, moduleInpaint)
         crop = crop_size(objectSettings) if objectSettings.get('boolCrop', True) else None
-        frames = render_frames(frame_cameras(objectSettings, objectCommon), objectCommon, crop, keep_on_device=keep_on_device)
+        frames = render_frames(frame_cameras(objectSettings, objectCommon), objectCommon, crop, keep_on_device=keep_on_device, out_size=out_size)
     if keep_on_device:
         return frames
     return [frames[i] for i in range(frames.shape[0])]

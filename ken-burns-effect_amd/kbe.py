@@ -10,6 +10,9 @@
         [--gif] [--gif-dither none|ordered]            (new: also write 3d_kbe.gif, an animated GIF encoded on the GPU: env KBE_GIF=1, KBE_GIF_DITHER)
         [--gif-width N] [--gif-fps F]                  (new, with --gif: the GIF N pixels wide -- reduced on the GPU, never enlarged -- and at about F
                                                         frames a second, every max(1, round(25 / F))-th frame: env KBE_GIF_WIDTH, KBE_GIF_FPS)
+        [--width N]                                    (new: every output -- the video, the PNG frames, the GIF -- N pixels wide, the height by the image's
+                                                        aspect ratio: the crop reduced on the GPU by an exact area average, never enlarged, so N is
+                                                        at most the crop's width; --gif-width is then at most N: env KBE_WIDTH)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -22,12 +25,12 @@ import numpy as np
 import torch
 
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
-                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=']
+                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=', 'width=']
 
 
 def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
-           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None,
+           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None, 'width': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -51,6 +54,12 @@ def parse(argv):
         if not (cfg['gif-width'].isdigit() and int(cfg['gif-width']) >= 1):
             raise SystemExit('--gif-width %s: a number of pixels, 1 or more' % cfg['gif-width'])
         cfg['gif-width'] = int(cfg['gif-width'])
+    if cfg['width'] is not None:
+        if not (cfg['width'].isdigit() and int(cfg['width']) >= 1):
+            raise SystemExit('--width %s: a number of pixels, 1 or more' % cfg['width'])
+        cfg['width'] = int(cfg['width'])
+        if cfg['gif-width'] is not None and cfg['gif-width'] > cfg['width']:
+            raise SystemExit('--gif-width %d: the frames are %d pixels wide (--width), and the GIF is only ever reduced' % (cfg['gif-width'], cfg['width']))
     if cfg['gif-fps'] is not None:
         try:
             cfg['gif-fps'] = float(cfg['gif-fps'])
@@ -100,7 +109,7 @@ def load_image(path, rgb):
 
 
 def main(argv=None):
-    from .pipeline import Pipeline
+    from .pipeline import Pipeline, width_size
     torch.set_grad_enabled(False)
     cfg, window = parse(sys.argv[1:] if argv is None else argv)
     if cfg['jpeg'] is not None:
@@ -115,12 +124,17 @@ def main(argv=None):
     if cfg['gif-width'] is not None and cfg['gif-width'] > image.shape[3]:
         raise SystemExit('--gif-width %d: the image is %d pixels wide, and the GIF is only ever reduced' % (cfg['gif-width'], image.shape[3]))
     zoom = windows_for(image.shape[3], image.shape[2], window, cfg['dolly'])
+    if cfg['width'] is not None:
+        try:                                                                # (before any network is built)
+            width_size(cfg['width'], image.shape[3], image.shape[2], zoom)
+        except ValueError as e:
+            raise SystemExit('--width %d: %s' % (cfg['width'], e))
     paths = [cfg['estim-path'], cfg['refine-path'], cfg['inpaint-path']] + ([cfg['inpaint-depth']] if cfg['inpaint-depth'] else [])
     pipe = Pipeline(model_paths=paths, dolly=cfg['dolly'], output_frames=cfg['write-frames'], pretrain=cfg['pretrained-refine'], d2=cfg['2d'],
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'],
-                    gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'])
+                    gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'])
     frames = pipe(image, zoom, cfg['out'], pretrained_estim=cfg['pretrained-estim'])
-    print('%d frames of %dx%d written to %s' % (len(frames), image.shape[3], image.shape[2], cfg['out']))
+    print('%d frames of %dx%d written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], cfg['out']))
 
 
 if __name__ == '__main__':

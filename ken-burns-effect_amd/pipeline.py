@@ -28,13 +28,18 @@ from .utils import load_models, resize_image
 
 class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
-                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None):
+                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
         # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
         # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
         # gif_fps: the GIF's frame rate, every max(1, round(25 / gif_fps))-th frame and the last; env KBE_GIF_FPS.  None and no env: the
         # frames' own size, every frame
         self.gif, self.gif_dither, self.gif_width, self.gif_fps = gif, gif_dither, gif_width, gif_fps
+        # width: every output -- the video, the PNG frames, the GIF, the frames returned -- that many pixels wide instead of the image's
+        # width, the height following the image's aspect ratio: the crop reduced on the GPU by an exact area average (crop_area.py), never
+        # enlarged, so at most the crop's size (common.crop_size of the zoom settings); env KBE_WIDTH.  gif_width is then taken against
+        # the reduced frames.  None and no env: the image's size, every file as before
+        self.width = width
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -144,6 +149,16 @@ class Pipeline():
             gif_wide, gif_every = gif_shape(getattr(self, 'gif_width', None), getattr(self, 'gif_fps', None))
             if gif_wide is not None and gif_wide > tensorImage.size(3):
                 raise ValueError('a GIF %d pixels wide from an image %d wide: the GIF is only ever reduced' % (gif_wide, tensorImage.size(3)))
+        # KBE_WIDTH (Pipeline(width=), kbe.py --width): looked at before any network runs as well
+        wide = out_width(getattr(self, 'width', None))
+        out_size = None
+        if wide is not None:
+            try:
+                out_size = width_size(wide, tensorImage.size(3), tensorImage.size(2), zoom_settings)
+            except ValueError as e:
+                raise ValueError('width %d: %s' % (wide, e)) from None
+            if gif_on and gif_wide is not None and gif_wide > out_size[0]:
+                raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif_wide, out_size[0]))
         with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
             self.estimate(tensorImage)
             if inpaint_depth:
@@ -159,7 +174,8 @@ class Pipeline():
             on_device = png_on_device or video_from_hbm or gif_on
             frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                               'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
-                                              'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device)
+                                              'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device,
+                                             **({} if out_size is None else {'out_size': out_size}))     # (without a width the call is what it was)
         if on_device:
             os.makedirs(output_path, exist_ok=True)
             # (the frames are in the INPUT's channel order, as below: the encoders read B, G, R unless --pretrained-estim)
@@ -306,6 +322,33 @@ def gif_shape(width=None, fps=None):
             raise ValueError("the GIF's frame rate (KBE_GIF_FPS, --gif-fps): frames a second, above 0")
         every = max(1, int(round(25.0 / fps)))
     return width, every
+
+
+def out_width(width=None):
+    """The width of every output in pixels, or None for the image's own: what Pipeline was told, else env KBE_WIDTH (kbe.py --width)."""
+    width = width if width is not None else os.environ.get('KBE_WIDTH') or None
+    if width is not None:
+        try:
+            whole = int(width)
+            width = whole if whole == float(width) else 0
+        except (TypeError, ValueError):
+            width = 0
+        if width < 1:
+            raise ValueError("the outputs' width (KBE_WIDTH, --width): a number of pixels, 1 or more")
+    return width
+
+
+def width_size(width, W, H, zoom_settings):
+    """(w, h) of outputs `width` wide from a W x H image: the height follows the image's aspect ratio (crop_area.size_for).  The frames are
+    the crop of the zoom settings (common.crop_size) reduced, never enlarged: a width, or its height, above the crop's is refused."""
+    from . import crop_area
+    crop_w, crop_h = (int(v) for v in common.crop_size(zoom_settings))
+    if width > crop_w:
+        raise ValueError('the crop is %d pixels wide: outputs are only ever reduced' % crop_w)
+    w, h = crop_area.size_for(W, H, width=width)
+    if h > crop_h:
+        raise ValueError('the outputs are then %d pixels high and the crop is %d pixels high: outputs are only ever reduced' % (h, crop_h))
+    return w, h
 
 
 def write_frames(frames_dir, frames_rgb, pngs=None):
