@@ -1,0 +1,57 @@
+/*
+ * kbe_dof.h -- C ABI of the depth-of-field blur of libkbe_hip.so (ken-burns-effect_amd/csrc/kbe_dof.hip; all of its arithmetic is defined in
+ * csrc/kbe_dof_block.h).  A header of its own beside kbe.h, kbe_gif.h, kbe_area.h and kbe_crop_area.h, with a version of its own: their
+ * entries and ABI numbers do not change with it.  Errors are reported as by kbe.h's entries: KBE_OK / KBE_E_INVALID / KBE_E_LAUNCH, the text
+ * through kbe_last_error().  Bound in Python by ken-burns-effect_amd/dof.py; common.render_frames(lens=...) is its user.
+ *
+ * A raw W x H frame, the fp32 depth of every one of its pixels (the cloud's depth attribute: plane 3 of kbe_render_frame's render_f32), a
+ * focus depth and an aperture: every pixel gets a blur radius r = min(max_radius, round(aperture |z - focus| / z)) -- computed without a
+ * division, every operation one IEEE rounding; a depth that is not finite or not > 0 gives 0 -- and every target pixel gathers the samples
+ * whose disc reaches it: a sample in front of the target, or level with it, spreads by its own radius, a sample behind it by no more than the
+ * target's own.  Samples outside the frame are skipped, a sample of radius e weighs 8192 / n(e) (n: the lattice points of the disc), and
+ * the weighted mean is rounded half up.  Integers after the radius; channels are not swapped.  The bytes are defined by
+ * csrc/kbe_dof_block.h executed serially on a CPU (tests/dof_check.cpp).
+ */
+#ifndef KBE_DOF_H
+#define KBE_DOF_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "kbe.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#if defined(__GNUC__)
+#define KBE_DOF_API __attribute__((visibility("default")))
+#else
+#define KBE_DOF_API
+#endif
+
+#define KBE_DOF_ABI_VERSION 1
+
+KBE_DOF_API int kbe_dof_abi_version(void);
+
+/* The frames of kbe_crop_area_u8's contract, blurred by their depths:
+ *   frames_u8: HOST array of n_frames DEVICE pointers to [H][stride_bytes] rows of 3-byte pixels, stride_bytes >= 3 W; 1 <= W, H <= 65535;
+ *              any n_frames >= 1 -- the entry cuts them into launches of at most 12 frames;
+ *   depth_f32: HOST array of n_frames DEVICE pointers to [H][depth_stride_floats] rows of fp32 depths, depth_stride_floats >= W;
+ *   focus:     HOST array of n_frames focus depths, each finite and > 0 (also as fp32: they and the aperture are converted once, here);
+ *   aperture:  finite, >= 0: the radius in pixels of a point at infinity; 0 returns the frames byte for byte;
+ *   max_radius: 0..16, the cap of every radius; 0 returns the frames byte for byte;
+ *   out_u8:    HOST array of n_frames DEVICE pointers to [H][out_stride_bytes] rows of 3-byte pixels, out_stride_bytes >= 3 W.  The bytes of
+ *              an output row beyond 3 W are not written.  No alignment is asked of any byte pointer or stride.  The byte range of an
+ *              output must not intersect the byte range of any source frame or depth plane of the call: a gather in place is wrong, not
+ *              merely slow, and is refused.
+ * Every argument is validated before anything is enqueued (KBE_E_INVALID, kbe_last_error names the entry and the argument); nothing is
+ * allocated, there is no scratch; all launches are asynchronous on `stream`. */
+KBE_DOF_API int kbe_dof_u8(const uint8_t* const* frames_u8, const float* const* depth_f32, int n_frames, int W, int H, int stride_bytes,
+                           int depth_stride_floats, const double* focus, double aperture, int max_radius, uint8_t* const* out_u8,
+                           int out_stride_bytes, kbe_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* KBE_DOF_H */

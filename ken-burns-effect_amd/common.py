@@ -319,7 +319,7 @@ def _prepared_cloud(K, objectCommon):
     return cached[1]
 
 
-def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_out=None, overlap=True, batch=None, out_size=None):
+def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_out=None, overlap=True, batch=None, out_size=None, lens=None):
     """The frame loop proper (common.py:238-257) for a list of (focal, shift3) cameras.
 
     One fused kernel sequence per frame on the resident packed cloud; frames land in one
@@ -335,7 +335,14 @@ def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_o
     frames are returned or fetched; host_out, overlap and batch do not apply.  What it costs: with crop=None the hole fill runs on the
     whole frame and not only inside the crop's window, and the fetch does not overlap the rendering.  Why it is right: a hole outside
     the window never sources a fill (deviation 7), so the pixels the patch reads are the ones the cropped route
-    would have produced."""
+    would have produced.
+
+    ``lens`` = dof.Lens(focus_from, focus_to, aperture, max_radius): depth of field.  The frames take a route of their own
+    (_render_lens): each is rendered on its own with its float render, blurred in HBM by the depth of its pixels (dof.apply), and only
+    then cropped and resized, reduced to ``out_size``, or left as it is; host_out, overlap and batch do not apply.  The sharded path does
+    not take the argument."""
+    if lens is not None:
+        return _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens)
     if out_size is not None:
         return _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device)
     K = _K()
@@ -380,19 +387,64 @@ def _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device):
     return host.numpy()
 
 
-def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False, out_size=None):
+def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens):
+    """render_frames(lens=...): groups of at most twelve frames, each frame rendered by K.render_frame with its float render (plane 3: the
+    depth of every pixel, hole-filled) and no fill rectangle -- the blur reads beyond the crop's window --, the group blurred where it lies
+    (dof.apply: one launch), then crop_area.reduce (out_size), K.crop_resize_u8 per frame (crop alone) or nothing more.  The focus
+    depth of frame i is dof.focus_path(focus_from, focus_to, n)[i]."""
+    from . import crop_area, dof
+    if out_size is not None and crop is None:
+        raise ValueError('render_frames(out_size=...) reduces the crop: it needs crop=(w, h)')
+    lens = dof.checked_lens(lens)
+    K = _K()
+    if getattr(K, 'name', '') != 'hip':
+        raise _native.KbeError('render_frames(lens=...) needs the float render of the HIP kernel set\'s render_frame; this kernel set is %r' % getattr(K, 'name', K))
+    W, H = objectCommon['intWidth'], objectCommon['intHeight']
+    state = _prepared_cloud(K, objectCommon)
+    device = objectCommon['tensorInpaPoints'].device
+    n = len(cameras)
+    focus = dof.focus_path(lens.focus_from, lens.focus_to, n)
+    w, h = (W, H) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=device)
+    group = max(1, min(n, dof.FRAMES_PER_GROUP))
+    raw = torch.empty(group, H, W, 3, dtype=torch.uint8, device=device)
+    render = torch.empty(group, 4, H, W, dtype=torch.float32, device=device)
+    for first in range(0, n, group):
+        count = min(group, n - first)
+        for k in range(count):
+            focal, shift3 = cameras[first + k]
+            K.render_frame(state, shift3, focal, objectCommon['dblBaseline'], render_f32=render[k], out=raw[k], fill_rect=None)
+        blurred = dof.apply(raw[:count], render[:count, 3], focus[first:first + count], lens.aperture, lens.max_radius)
+        if out_size is not None:
+            out[first:first + count].copy_(crop_area.reduce(blurred, crop, out_size))
+        elif crop is not None:
+            for k in range(count):
+                out[first + k].copy_(K.crop_resize_u8(blurred[k], crop[0], crop[1]))
+        else:
+            out[first:first + count].copy_(blurred)
+    if keep_on_device:
+        return out
+    host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return host.numpy()
+
+
+def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False, out_size=None, lens=None):
     """Renders the camera path ``dblSteps`` between two crop windows (common.py:172-263).
 
     objectSettings: dblSteps, objectFrom/objectTo {dblCenterU, dblCenterV, intCropWidth,
     intCropHeight}, boolInpaint (default True), dolly.  Returns a list of uint8 HxWx3 frames.
     Optional key ``boolCrop`` (default True): apply the crop + resize of :256-257.  ``keep_on_device``: the frames stay in HBM and
     come back as one uint8 [n,H,W,3] device tensor (for the device-side Motion-JPEG encoder).  ``out_size`` = (w, h): frames of that size,
-    the crop reduced on the GPU and never enlarged (render_frames(out_size=...)); it needs the crop (``boolCrop``)."""
+    the crop reduced on the GPU and never enlarged (render_frames(out_size=...)); it needs the crop (``boolCrop``).  ``lens``: depth of
+    field (render_frames(lens=...))."""
     with on_device_of(objectCommon['tensorRawPoints']):
         if 'boolInpaint' not in objectSettings or objectSettings['boolInpaint'] == True:   # noqa: E712
             build_pointcloud(objectSettings, objectCommon, moduleInpaint)
         crop = crop_size(objectSettings) if objectSettings.get('boolCrop', True) else None
-        frames = render_frames(frame_cameras(objectSettings, objectCommon), objectCommon, crop, keep_on_device=keep_on_device, out_size=out_size)
+        frames = render_frames(frame_cameras(objectSettings, objectCommon), objectCommon, crop, keep_on_device=keep_on_device, out_size=out_size,
+                               **({} if lens is None else {'lens': lens}))
     if keep_on_device:
         return frames
     return [frames[i] for i in range(frames.shape[0])]

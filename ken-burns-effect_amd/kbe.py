@@ -13,6 +13,10 @@
         [--width N]                                    (new: every output -- the video, the PNG frames, the GIF -- N pixels wide, the height by the image's
                                                         aspect ratio: the crop reduced on the GPU by an exact area average, never enlarged, so N is
                                                         at most the crop's width; --gif-width is then at most N: env KBE_WIDTH)
+        [--aperture A] [--focus U,V] [--focus-to U,V]  (new: depth of field, a lens blur on the GPU from each frame's depth -- A is the blur radius in
+                                                        pixels of a point at infinity, above 0; what lies at the depth of pixel U,V of the photo
+                                                        stays sharp (default: the centre of the end window), and with --focus-to the focus is pulled
+                                                        to that pixel's depth over the clip: env KBE_APERTURE, KBE_FOCUS, KBE_FOCUS_TO)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -25,12 +29,12 @@ import numpy as np
 import torch
 
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
-                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=', 'width=']
+                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=', 'width=', 'aperture=', 'focus=', 'focus-to=']
 
 
 def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
-           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None, 'width': None,
+           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None, 'width': None, 'aperture': None, 'focus': None, 'focus-to': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -60,6 +64,15 @@ def parse(argv):
         cfg['width'] = int(cfg['width'])
         if cfg['gif-width'] is not None and cfg['gif-width'] > cfg['width']:
             raise SystemExit('--gif-width %d: the frames are %d pixels wide (--width), and the GIF is only ever reduced' % (cfg['gif-width'], cfg['width']))
+    if cfg['aperture'] is not None or cfg['focus'] is not None or cfg['focus-to'] is not None:
+        from .pipeline import lens_request
+        for name in ('focus', 'focus-to'):
+            if cfg[name] is not None and cfg['aperture'] is None:
+                raise SystemExit('--%s %s: only with --aperture' % (name, cfg[name]))
+        try:
+            cfg['aperture'], cfg['focus'], cfg['focus-to'] = lens_request(cfg['aperture'], cfg['focus'], cfg['focus-to'])
+        except ValueError as e:
+            raise SystemExit('--%s' % str(e).replace('_', '-', 1) if str(e).startswith('focus') else '--aperture %s: %s' % (cfg['aperture'], e))
     if cfg['gif-fps'] is not None:
         try:
             cfg['gif-fps'] = float(cfg['gif-fps'])
@@ -109,7 +122,7 @@ def load_image(path, rgb):
 
 
 def main(argv=None):
-    from .pipeline import Pipeline, width_size
+    from .pipeline import Pipeline, lens_points, width_size
     torch.set_grad_enabled(False)
     cfg, window = parse(sys.argv[1:] if argv is None else argv)
     if cfg['jpeg'] is not None:
@@ -129,10 +142,15 @@ def main(argv=None):
             width_size(cfg['width'], image.shape[3], image.shape[2], zoom)
         except ValueError as e:
             raise SystemExit('--width %d: %s' % (cfg['width'], e))
+    if cfg['aperture'] is not None:
+        try:                                                                # (before any network is built as well)
+            lens_points((cfg['aperture'], cfg['focus'], cfg['focus-to']), image.shape[3], image.shape[2], zoom)
+        except ValueError as e:
+            raise SystemExit('--%s' % str(e).replace('_', '-', 1))
     paths = [cfg['estim-path'], cfg['refine-path'], cfg['inpaint-path']] + ([cfg['inpaint-depth']] if cfg['inpaint-depth'] else [])
     pipe = Pipeline(model_paths=paths, dolly=cfg['dolly'], output_frames=cfg['write-frames'], pretrain=cfg['pretrained-refine'], d2=cfg['2d'],
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'],
-                    gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'])
+                    gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'])
     frames = pipe(image, zoom, cfg['out'], pretrained_estim=cfg['pretrained-estim'])
     print('%d frames of %dx%d written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], cfg['out']))
 

@@ -11,6 +11,7 @@ weights of ``Semantics`` come from a file (``semantics_path``) instead of a torc
 video through an ``ffmpeg`` binary if one is on PATH (OpenCV / moviepy are not dependencies) --
 otherwise the ``.mp4`` holds Motion-JPEG (ISO base media file written here, no external encoder).  Returns the frame list.
 """
+import math
 import os
 import shutil
 import subprocess
@@ -28,7 +29,7 @@ from .utils import load_models, resize_image
 
 class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
-                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None):
+                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
         # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
         # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
@@ -40,6 +41,12 @@ class Pipeline():
         # enlarged, so at most the crop's size (common.crop_size of the zoom settings); env KBE_WIDTH.  gif_width is then taken against
         # the reduced frames.  None and no env: the image's size, every file as before
         self.width = width
+        # aperture: depth of field -- the blur radius, in pixels of the raw frame, of a point at infinity, above 0 and finite; what lies at the
+        # focus depth stays sharp (dof.py, common.render_frames(lens=)); env KBE_APERTURE.  focus = (u, v): the pixel of the photo to focus on
+        # (default: the centre of the end window); focus_to = (u, v): the focus is pulled there over the clip, linearly in 1 / depth (default:
+        # it stays); env KBE_FOCUS, KBE_FOCUS_TO as "U,V".  The depths are read from the estimated depth.  None and no env: no lens, every
+        # file as before
+        self.aperture, self.focus, self.focus_to = aperture, focus, focus_to
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -159,6 +166,11 @@ class Pipeline():
                 raise ValueError('width %d: %s' % (wide, e)) from None
             if gif_on and gif_wide is not None and gif_wide > out_size[0]:
                 raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif_wide, out_size[0]))
+        # KBE_APERTURE, KBE_FOCUS, KBE_FOCUS_TO (Pipeline(aperture=, focus=, focus_to=), kbe.py --aperture --focus --focus-to): looked at
+        # before any network runs as well; the focus DEPTHS are read from the estimated depth below
+        lens_at = lens_request(getattr(self, 'aperture', None), getattr(self, 'focus', None), getattr(self, 'focus_to', None))
+        if lens_at is not None:
+            lens_at = lens_points(lens_at, tensorImage.size(3), tensorImage.size(2), zoom_settings)
         with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
             self.estimate(tensorImage)
             if inpaint_depth:
@@ -172,10 +184,15 @@ class Pipeline():
             png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
             video_from_hbm = jpeg_on_device and (png_on_device or not self.output_frames)
             on_device = png_on_device or video_from_hbm or gif_on
+            lens = {}
+            if lens_at is not None:
+                from . import dof
+                aperture, near, far = lens_at
+                lens = {'lens': dof.Lens(dof.focus_depth(self.objectCommon['tensorRawDepth'], *near), dof.focus_depth(self.objectCommon['tensorRawDepth'], *far), aperture)}
             frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                               'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                               'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device,
-                                             **({} if out_size is None else {'out_size': out_size}))     # (without a width the call is what it was)
+                                             **({} if out_size is None else {'out_size': out_size}), **lens)     # (without a width or a lens the call is what it was)
         if on_device:
             os.makedirs(output_path, exist_ok=True)
             # (the frames are in the INPUT's channel order, as below: the encoders read B, G, R unless --pretrained-estim)
@@ -349,6 +366,55 @@ def width_size(width, W, H, zoom_settings):
     if h > crop_h:
         raise ValueError('the outputs are then %d pixels high and the crop is %d pixels high: outputs are only ever reduced' % (h, crop_h))
     return w, h
+
+
+def _focus_point(value, what):
+    """(u, v) of "U,V" or a pair, or ValueError."""
+    try:
+        u, v = (value.split(',') if isinstance(value, str) else value)
+        u, v = float(u), float(v)
+        if not (math.isfinite(u) and math.isfinite(v)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError('%s %s: U,V, a pixel of the photo' % (what, value if isinstance(value, str) else (value,))) from None
+    return u, v
+
+
+def lens_request(aperture=None, focus=None, focus_to=None):
+    """(aperture, focus or None, focus_to or None), the points as (u, v), or None for no lens: what Pipeline was told, else env KBE_APERTURE,
+    KBE_FOCUS, KBE_FOCUS_TO (kbe.py --aperture, --focus, --focus-to).  The aperture is pixels, above 0 and finite; a focus point without an
+    aperture is refused."""
+    aperture = aperture if aperture is not None else os.environ.get('KBE_APERTURE') or None
+    focus = focus if focus is not None else os.environ.get('KBE_FOCUS') or None
+    focus_to = focus_to if focus_to is not None else os.environ.get('KBE_FOCUS_TO') or None
+    if aperture is None:
+        for value, what in ((focus, 'focus (KBE_FOCUS, --focus)'), (focus_to, 'focus_to (KBE_FOCUS_TO, --focus-to)')):
+            if value is not None:
+                raise ValueError('%s: only with an aperture (KBE_APERTURE, --aperture)' % what)
+        return None
+    try:
+        aperture = float(aperture)
+    except (TypeError, ValueError):
+        aperture = 0.0
+    if not (math.isfinite(aperture) and aperture > 0.0):
+        raise ValueError('the aperture (KBE_APERTURE, --aperture): pixels, a finite number above 0')
+    return aperture, None if focus is None else _focus_point(focus, 'focus'), None if focus_to is None else _focus_point(focus_to, 'focus_to')
+
+
+def lens_points(request, W, H, zoom_settings):
+    """(aperture, (u, v) of the first frame's focus, (u, v) of the last frame's) from lens_request's answer for a W x H image, or None.  The
+    default focus is the centre of the end window; the default focus_to is the focus.  A point outside the image is refused."""
+    if request is None:
+        return None
+    aperture, focus, focus_to = request
+    if focus is None:
+        focus = (float(zoom_settings['objectTo']['dblCenterU']), float(zoom_settings['objectTo']['dblCenterV']))
+    if focus_to is None:
+        focus_to = focus
+    for (u, v), what in ((focus, 'focus'), (focus_to, 'focus_to')):
+        if not (0.0 <= u <= W - 1 and 0.0 <= v <= H - 1):
+            raise ValueError('%s %g,%g: the image is %dx%d: a pixel of the photo, 0..%d and 0..%d' % (what, u, v, W, H, W - 1, H - 1))
+    return aperture, focus, focus_to
 
 
 def write_frames(frames_dir, frames_rgb, pngs=None):
