@@ -6,11 +6,12 @@
  *
  * A raw W x H frame, the fp32 depth of every one of its pixels (the cloud's depth attribute: plane 3 of kbe_render_frame's render_f32), a
  * focus depth and an aperture: every pixel gets a blur radius r = min(max_radius, round(aperture |z - focus| / z)) -- computed without a
- * division, every operation one IEEE rounding; a depth that is not finite or not > 0 gives 0 -- and every target pixel gathers the samples
- * whose disc reaches it: a sample in front of the target, or level with it, spreads by its own radius, a sample behind it by no more than the
- * target's own.  Samples outside the frame are skipped, a sample of radius e weighs 8192 / n(e) (n: the lattice points of the disc), and
- * the weighted mean is rounded half up.  Integers after the radius; channels are not swapped.  The bytes are defined by
- * csrc/kbe_dof_block.h executed serially on a CPU (tests/dof_check.cpp).
+ * division, every operation one IEEE rounding; a depth that is not finite or not > 0 gives 0; subnormal depths and a subnormal focus are
+ * depths like any other and are not flushed to zero -- and every target pixel gathers the samples whose disc reaches it: a sample in front
+ * of the target, or level with it, spreads by its own radius, a sample behind it by no more than the target's own.  Samples outside the
+ * frame are skipped, a sample of radius e weighs 8192 / n(e) (n: the lattice points of the disc), and the weighted mean is rounded half up.
+ * Integers after the radius; channels are not swapped.  The bytes are defined by csrc/kbe_dof_block.h executed serially on a CPU
+ * (tests/dof_check.cpp).
  */
 #ifndef KBE_DOF_H
 #define KBE_DOF_H

@@ -12,7 +12,9 @@
 //       r = the number of j in 1..R with lhs >= (j - 0.5) * z      (one fp32 multiplication each; j - 0.5 is exact)
 //     which is min(R, round(A |z - zf| / z)) stated so that every operation is a single IEEE rounding and none a multiply-add a compiler
 //     could contract (-ffp-contract=off is part of the build all the same).  A depth that is not finite or not > 0 -- a hole nothing could
-//     fill, NaN, +-inf, 0, a negative value -- gives r = 0.
+//     fill, NaN, +-inf, 0, a negative value -- gives r = 0.  A subnormal z or zf is a depth like any other (z > 0, finite): the operations
+//     above keep their one rounding in the subnormal range, so neither compilation may flush fp32 denormals to zero (no -ffast-math, no
+//     -fgpu-flush-denormals-to-zero; hipcc's default for gfx9 keeps them).  zf = 1e-40, A = 3: z = 3e-40, 1.5e-40, 2.5e-40 give 2, 1, 2.
 // (2) The gather.  For a target pixel p and every sample pixel q INSIDE the frame with |dx|, |dy| <= R (no border is repeated):
 //       e = r(q)                 when z(q) <= z(p), a plain fp32 comparison: a sample in front of the target, or level with it;
 //       e = min(r(q), r(p))      otherwise: a sample behind the target never spreads further over it than the target is blurred itself;

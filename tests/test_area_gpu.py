@@ -1,7 +1,6 @@
 """The exact area-average reduction on the GPU (include/kbe_area.h; kernel: csrc/kbe_area.hip): kbe_area_reduce_u8 byte for byte against the
 NumPy twin (tests/area_cases.py) under guard bands, padded strides, an unaligned output and argument checks, and the host side built on it
 (area.reduce, gif.write_gif(size=, every=), Pipeline under KBE_GIF_WIDTH)."""
-import ctypes
 import io
 
 import numpy as np
@@ -11,8 +10,9 @@ from PIL import Image
 
 import area_cases as ac
 import encoder_gpu as eg
+import filter_gpu as fg
 import gif_cases as gc
-from guarded import SENTINEL, Guard
+from guarded import SENTINEL
 
 pytestmark = pytest.mark.gpu
 
@@ -30,31 +30,7 @@ def rendered():
     return eg.rendered(eg.kernels())
 
 
-def stream():
-    from ken_burns_effect_amd import _native
-    return _native._stream()
-
-
-def run(A, frames, w, h, pad=0, out_pad=0, shift=0, change=None):
-    """kbe_area_reduce_u8 on uint8 frames [n,H,W,3]: the source's rows `pad` bytes apart beyond their pixels, the output's rows `out_pad`, the
-    output `shift` bytes off its allocation's start, in a guarded allocation of its own per frame, every byte the sentinel.  change(args): the
-    last word on the argument list -- a dict by the header's names.  -> (rc, [n, h', out_stride] bytes: the outputs as they lie, w', h')."""
-    frames = np.asarray(frames)
-    n, H, W, _ = frames.shape
-    rows = np.full((n, H, 3 * W + pad), 0x5A, np.uint8)
-    rows[:, :, :3 * W] = frames.reshape(n, H, 3 * W)
-    src = torch.from_numpy(rows).cuda()
-    guard = Guard()
-    out_stride = 3 * w + out_pad
-    outs = [guard.full((h * out_stride,), SENTINEL, torch.uint8, 'cuda', shift=shift) for _ in range(n)]
-    args = dict(frames_u8=(ctypes.c_void_p * n)(*[src.data_ptr() + i * H * (3 * W + pad) for i in range(n)]), n_frames=n, W=W, H=H, stride_bytes=3 * W + pad,
-                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), w=w, h=h, out_stride_bytes=out_stride, stream=stream())
-    if change:
-        change(args)
-    rc = A._raw('kbe_area_reduce_u8', *args.values())
-    torch.cuda.synchronize()
-    guard.check()
-    return rc, np.stack([o.cpu().numpy().reshape(h, out_stride) for o in outs])
+stream, run = fg.stream, fg.run_area                  # (the raw call on guarded buffers: tests/filter_gpu.py)
 
 
 def assert_reduced(A, frames, w, h, want, **kw):

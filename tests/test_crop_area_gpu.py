@@ -12,7 +12,7 @@ from PIL import Image
 
 import crop_area_cases as cc
 import encoder_gpu as eg
-from guarded import Guard
+import filter_gpu as fg
 
 pytestmark = pytest.mark.gpu
 POISONS = (0x00, 0xFF)
@@ -27,34 +27,7 @@ def CA():
     return crop_area
 
 
-def stream():
-    from ken_burns_effect_amd import _native
-    return _native._stream()
-
-
-def run(CA, frames, crop, size, pad=0, out_pad=0, shift=0, src_shift=0, change=None, poison=0xFF):
-    """kbe_crop_area_u8 on uint8 frames [n,H,W,3]: the source `src_shift` bytes off its allocation's start and its rows `pad` bytes apart beyond
-    their pixels, the output's rows `out_pad`, the output `shift` bytes off its allocation's start, in a guarded allocation of its own per
-    frame, every byte the poison.  change(args): the last word on the argument list -- a dict by the header's names.
-    -> (rc, [n, h, out_stride] bytes: the outputs as they lie)."""
-    frames = np.asarray(frames)
-    n, H, W, _ = frames.shape
-    (cw, ch), (w, h) = crop, size
-    rows = np.full((n, H, 3 * W + pad), 0x5A, np.uint8)
-    rows[:, :, :3 * W] = frames.reshape(n, H, 3 * W)
-    guard = Guard(poison)
-    src = guard.empty((rows.size,), torch.uint8, 'cuda', shift=src_shift)
-    src.copy_(torch.from_numpy(rows.reshape(-1)))
-    out_stride = 3 * w + out_pad
-    outs = [guard.empty((h * out_stride,), torch.uint8, 'cuda', shift=shift) for _ in range(n)]
-    args = dict(frames_u8=(ctypes.c_void_p * n)(*[src.data_ptr() + i * H * (3 * W + pad) for i in range(n)]), n_frames=n, W=W, H=H, stride_bytes=3 * W + pad, crop_w=cw, crop_h=ch,
-                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), w=w, h=h, out_stride_bytes=out_stride, stream=stream())
-    if change:
-        change(args)
-    rc = CA._raw('kbe_crop_area_u8', *args.values())
-    torch.cuda.synchronize()
-    guard.check()                                                       # exactly h * out_stride bytes between untouched bands
-    return rc, np.stack([o.cpu().numpy().reshape(h, out_stride) for o in outs])
+stream, run = fg.stream, fg.run_crop_area             # (the raw call on guarded buffers: tests/filter_gpu.py)
 
 
 def assert_reduced(CA, frames, crop, size, want, poisons=POISONS, **kw):

@@ -1,7 +1,6 @@
 """The depth-of-field blur on the GPU (include/kbe_dof.h; kernel: csrc/kbe_dof.hip): kbe_dof_u8 byte for byte against the NumPy twin
 (tests/dof_cases.py) under guard bands and both poisons, at the shapes where the kernel can go wrong, with padded strides, unaligned pointers,
 special depths and every refusal, and the host side built on it (dof.apply, common.render_frames(lens=), Pipeline(aperture=))."""
-import ctypes
 import warnings
 
 import numpy as np
@@ -11,8 +10,8 @@ from PIL import Image
 
 import dof_cases as dc
 import encoder_gpu as eg
+import filter_gpu as fg
 import gif_cases as gc
-from guarded import Guard
 
 pytestmark = pytest.mark.gpu
 POISONS = (0x00, 0xFF)
@@ -26,40 +25,7 @@ def DOF():
     return dof
 
 
-def stream():
-    from ken_burns_effect_amd import _native
-    return _native._stream()
-
-
-def run(DOF, frames, depths, focus, A, R, pad=0, z_pad=0, out_pad=0, shift=0, src_shift=0, gap=0, change=None, poison=0xFF):
-    """kbe_dof_u8 on uint8 frames [n,H,W,3] and float32 depths [n,H,W]: the source `src_shift` bytes off its allocation's start, its rows `pad`
-    bytes apart beyond their pixels and its frames `gap` bytes apart, the depth rows `z_pad` floats apart, the output's rows `out_pad` bytes,
-    the output `shift` bytes off its allocation's start, in a guarded allocation of its own per frame, every byte the poison.
-    change(args): the last word on the argument list -- a dict by the header's names.  -> (rc, [n, H, out_stride] bytes: the outputs as they lie)."""
-    frames, depths = np.asarray(frames), np.asarray(depths, np.float32)
-    n, H, W, _ = frames.shape
-    rows = np.full((n, H * (3 * W + pad) + gap), 0x5A, np.uint8)
-    rows[:, :H * (3 * W + pad)].reshape(n, H, 3 * W + pad)[:, :, :3 * W] = frames.reshape(n, H, 3 * W)
-    planes = np.full((n, H, W + z_pad), -7.0, np.float32)
-    planes[:, :, :W] = depths
-    guard = Guard(poison)
-    src = guard.empty((rows.size,), torch.uint8, 'cuda', shift=src_shift)
-    src.copy_(torch.from_numpy(rows.reshape(-1)))
-    z = guard.empty((planes.size,), torch.float32, 'cuda')
-    z.copy_(torch.from_numpy(planes.reshape(-1)))
-    out_stride = 3 * W + out_pad
-    outs = [guard.empty((H * out_stride,), torch.uint8, 'cuda', shift=shift) for _ in range(n)]
-    args = dict(frames_u8=(ctypes.c_void_p * n)(*[src.data_ptr() + i * rows.shape[1] for i in range(n)]),
-                depth_f32=(ctypes.c_void_p * n)(*[z.data_ptr() + 4 * i * H * (W + z_pad) for i in range(n)]), n_frames=n, W=W, H=H, stride_bytes=3 * W + pad,
-                depth_stride_floats=W + z_pad, focus=(ctypes.c_double * n)(*[float(f) for f in focus]), aperture=float(A), max_radius=R,
-                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), out_stride_bytes=out_stride, stream=stream())
-    if change:
-        change(args)
-    rc = DOF._raw('kbe_dof_u8', *args.values())
-    torch.cuda.synchronize()
-    guard.check()                                                       # exactly H * out_stride bytes between untouched bands
-    assert np.array_equal(src.cpu().numpy(), rows.reshape(-1)) and np.array_equal(z.cpu().numpy().view(np.uint8), planes.reshape(-1).view(np.uint8))          # the inputs are only read (bit for bit: NaNs among them)
-    return rc, np.stack([o.cpu().numpy().reshape(H, out_stride) for o in outs])
+stream, run = fg.stream, fg.run_dof                   # (the raw call on guarded buffers: tests/filter_gpu.py)
 
 
 def assert_blurred(DOF, frames, depths, focus, A, R, want, poisons=POISONS, **kw):

@@ -87,6 +87,19 @@ def test_the_specials_give_radius_0():
     assert dc.twin_radius(mixed, 120.0, 1e38, 16).tolist() == dc.header_radius(mixed, 120.0, 1e38, 16).tolist() == [0, 16, 0, 16, 16]
 
 
+def test_the_radius_of_subnormal_depths():
+    """Depths and a focus below the smallest normal fp32 number are valid (z > 0, finite) and nothing flushes them: every operation is still one
+    IEEE rounding, so zf = 1e-40 and A = 3 give z = 3e-40, 1.5e-40 and 2.5e-40 the radii round(3 (z - zf) / z) = 2, 1, 2; the smallest normal
+    number gets 3.  The twin and the header agree; a build that flushed them to zero would give 0 (z = 0 is no depth)."""
+    z = np.array([3e-40, 1.5e-40, 2.5e-40, 1.1754944e-38], np.float32)
+    assert (z > 0).all() and (z[:3] < np.finfo(np.float32).tiny).all() and z[3] == np.finfo(np.float32).tiny and 0 < np.float32(1e-40) < z.min()
+    for A, want in ((3.0, [2, 1, 2, 3]), (1.0, [1, 0, 1, 1]), (20.0, [13, 7, 12, 16])):
+        assert dc.twin_radius(z, 1e-40, A, 16).tolist() == dc.header_radius(z, 1e-40, A, 16).tolist() == want, A
+    # a subnormal depth against a normal focus, and a normal depth against a subnormal focus
+    assert dc.twin_radius(z, 120.0, 20.0, 16).tolist() == dc.header_radius(z, 120.0, 20.0, 16).tolist() == [16] * 4
+    assert dc.twin_radius(np.array([64.0], np.float32), 1e-40, 7.0, 16).tolist() == dc.header_radius(np.array([64.0], np.float32), 1e-40, 7.0, 16).tolist() == [7]
+
+
 # -- the properties that follow -------------------------------------------------------------------
 def test_no_aperture_no_radius_or_everything_in_focus_returns_the_frame():
     W, H = dc.FRAMES[0]

@@ -1,0 +1,100 @@
+"""The three byte-frame filters on the GPU (kbe_area_reduce_u8, kbe_crop_area_u8, kbe_dof_u8) where their own test modules do not reach: every
+alignment class of the tile store and of the row fetch, which each kernel has a copy of; the sides' limit of 65535; and the radius of the blur
+as the device computes it, at its ties, at products that overflow and on subnormal depths.  Byte for byte against the twins, or at the sides'
+limit against references that work there (tests/filter_sweep_cases.py; what they rest on: tests/test_filter_sweeps.py), every buffer from
+guarded.Guard on both poisons."""
+import numpy as np
+import pytest
+import torch
+
+import dof_cases as dc
+import filter_gpu as fg
+import filter_sweep_cases as fc
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def entries():
+    """entry -> (its module, its raw call)"""
+    from ken_burns_effect_amd import area, crop_area, dof
+    assert torch.cuda.is_available(), 'GPU tests need a GPU'
+    for module in (area, crop_area, dof):
+        module.load()
+    return {'area': (area, fg.run_area), 'crop_area': (crop_area, fg.run_crop_area), 'dof': (dof, fg.run_dof)}
+
+
+def assert_bytes(entries, entry, args, want, poison, **kw):
+    """One call on guarded buffers full of the poison, every allocation on a multiple of 512 and the buffers their shifts off it: the expected
+    bytes, the rows' padding unwritten, the bands intact (the raw call checks them)."""
+    module, run = entries[entry]
+    rc, got = run(module, *args, poison=poison, aligned=True, **kw)
+    n, h, w, _ = want.shape
+    assert rc == 0
+    assert np.array_equal(got[:, :, :3 * w].reshape(n, h, w, 3), want), (entry, w, h, poison, kw)
+    assert (got[:, :, 3 * w:] == poison).all(), (entry, w, h, poison, kw)
+
+
+# -- 1. the alignment classes ------------------------------------------------------------------------
+@pytest.mark.parametrize('poison', fg.POISONS, ids=hex)
+@pytest.mark.parametrize('entry, variant', fc.STORE_SWEEPS, ids=str)
+def test_every_lead_at_every_tile_width(entries, entry, variant, poison):
+    """16 output rows an odd number of bytes apart -- every address mod 16 -- at every width 1 .. 64 of a single tile, and with a second and a
+    third tile behind it: all 1024 classes of the store (tests/test_filter_sweeps.py), one call per width."""
+    for w in fc.store_widths(entry, variant):
+        args, kw, want = fc.store_case(entry, variant, w)
+        assert want.shape == (1, fc.STORE_ROWS, w, 3) and 3 * w + kw['out_pad'] == fc.store_stride(w)
+        assert_bytes(entries, entry, args, want, poison, **kw)
+
+
+@pytest.mark.parametrize('poison', fg.POISONS, ids=hex)
+@pytest.mark.parametrize('entry, variant', fc.FETCH_SWEEPS, ids=str)
+def test_every_shift_at_every_length(entries, entry, variant, poison):
+    """Source rows an odd number of bytes apart, the source 0, 1, 2 and 3 bytes off its allocation, four consecutive widths: all 16 classes of
+    the aligned-dword fetch (tests/test_filter_sweeps.py)."""
+    for W in fc.FETCH_WIDTHS[entry]:
+        args, kw, want = fc.fetch_case(entry, variant, W)
+        for src_shift in fc.SRC_SHIFTS:
+            assert_bytes(entries, entry, args, want, poison, src_shift=src_shift, **kw)
+
+
+# -- 2. the sides' limit -------------------------------------------------------------------------------
+@pytest.mark.parametrize('poison', fg.POISONS, ids=hex)
+@pytest.mark.parametrize('name', fc.LIMITS)
+def test_area_at_the_sides_limit(entries, name, poison):
+    """65535 x 2 and 2 x 65535 to themselves, to one pixel less, to just over half, to a ratio that is no integer and to one pixel: 1024 tiles
+    across or 16384 down, span_end within 0.002 % of 2^32.  The expected bytes are the prefix sums'."""
+    frame = fc.limit_frame(name)
+    for w, h in fc.area_limit_targets(name):
+        assert_bytes(entries, 'area', (frame, w, h), fc.exact_reduce(frame, w, h), poison, out_pad=1)
+
+
+@pytest.mark.parametrize('poison', fg.POISONS, ids=hex)
+@pytest.mark.parametrize('name', fc.LIMITS)
+def test_crop_area_at_the_sides_limit(entries, name, poison):
+    """Crops of those frames that start on a half pixel along the long side, on whole pixels, and that are the frame's own sides, each to the
+    patch itself, to just over half of it and to one pixel."""
+    frame = fc.limit_frame(name)
+    for crop, size in fc.crop_limit_cases(name):
+        assert_bytes(entries, 'crop_area', (frame, crop, size), fc.exact_crop_reduce(frame, crop, size), poison, out_pad=1)
+
+
+@pytest.mark.parametrize('poison', fg.POISONS, ids=hex)
+@pytest.mark.parametrize('name', fc.LIMITS)
+def test_dof_at_the_sides_limit(entries, name, poison):
+    """dof_cases' depths at 65535 x 2 and 2 x 65535, R = 16: the header's bytes (the twin's: tests/test_filter_sweeps.py)."""
+    args = (fc.limit_frame(name), fc.limit_depth(name), dc.focus_of(1), dc.APERTURE, 16)
+    assert_bytes(entries, 'dof', args, fc.limit_blur(name), poison, out_pad=1)
+
+
+# -- 3. the radius as the device computes it -------------------------------------------------------------
+@pytest.mark.parametrize('name', fc.RADIUS_ORDER)
+def test_the_marks_spread_by_the_radius_of_the_definition(entries, name):
+    """A black frame two tiles each way with radius 0 and three white marks in front of it whose depths are under test -- at a tie, one ulp to
+    either side of it, with the aperture one ulp below; where A t and (j - 0.5) z overflow; subnormal -- across the tiles' borders.  The twin
+    and the header agree on the marks' radii, the twin's bytes would be others at a radius one off (filter_sweep_cases.radius_case), and the
+    device's bytes are the twin's."""
+    frame, depth, want = fc.radius_case(name)
+    zf, A = fc.RADIUS_CASES[name][:2]
+    for poison in fg.POISONS:
+        assert_bytes(entries, 'dof', (frame, depth, [zf], A, 16), want, poison, out_pad=5, pad=2, z_pad=1)
