@@ -33,6 +33,9 @@ def stream():
     return _native._stream()
 
 
+current_stream = stream            # (run takes a `stream` of its own)
+
+
 def on_device(a):
     return a if torch.is_tensor(a) else torch.from_numpy(np.array(a)).cuda()           # (a copy: the cases' arrays are read-only)
 
@@ -69,12 +72,12 @@ def pointers_of(frames, n=None):
     return (ctypes.c_void_p * max(n, 1))(*[frames.data_ptr() + i * H * Wt * 3 for i in range(n)])
 
 
-def run(K, enc, frames, own, cap, W=None, n=None, shift=0, status_before=7, change=None):
+def run(K, enc, frames, own, cap, W=None, n=None, shift=0, status_before=7, change=None, stream=None):
     """The entry on a uint8 device tensor [n,H,Wt,3] (W <= Wt: the rows' stride is Wt's) with a buffer of `cap` bytes (`shift` bytes off its
     allocation's start) followed by GUARD bytes, everything the call may write filled with sentinels first; own: the values of enc.names.
     The scratch is exactly kbe_<fmt>_scratch_bytes, rounded up only to the 8 bytes its alignment check asks for, every byte of it 0xFF, and
     like the offsets and the status word between two guard bands (tests/guarded.py) that the call must leave alone.  change(args): the last
-    word on the argument list -- a dict by the header's names.
+    word on the argument list -- a dict by the header's names; stream: the kbe_stream_t of the call (default: torch's current stream).
     -> (rc, offsets, status, the buffer with its guard, whether the scratch still holds its poison)."""
     raw, lib = enc.via(K)
     count, H, Wt, _ = frames.shape
@@ -87,7 +90,7 @@ def run(K, enc, frames, own, cap, W=None, n=None, shift=0, status_before=7, chan
     offsets = guard.full((max(n, 1) + 1,), -1, torch.int64, 'cuda')
     status = guard.full((1,), status_before, torch.int32, 'cuda')
     args = dict(frames_u8=pointers_of(frames, n), n_frames=n, W=W, H=H, stride_bytes=3 * Wt, **dict(zip(enc.names, own)), scratch=scratch.data_ptr(),
-                out=out.data_ptr() + shift, cap=cap, offsets=offsets.data_ptr(), status=status.data_ptr(), stream=stream())
+                out=out.data_ptr() + shift, cap=cap, offsets=offsets.data_ptr(), status=status.data_ptr(), stream=current_stream() if stream is None else stream)
     assert len(own) == len(enc.names)
     if change:
         change(args)

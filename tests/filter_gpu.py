@@ -17,6 +17,9 @@ def stream():
     return _native._stream()
 
 
+current_stream = stream            # (the raw calls below take a `stream` of their own: the kbe_stream_t of the call, default torch's current stream)
+
+
 def _padded_rows(frames, pad, gap=0):
     """uint8 [n,H,W,3] -> uint8 [n, H * (3 W + pad) + gap]: the rows `pad` bytes apart beyond their pixels, the frames `gap` bytes, 0x5A between."""
     n, H, W, _ = frames.shape
@@ -36,7 +39,7 @@ def _placed(guard, rows, src_shift, outs_of, shift, aligned):
     return src, outs
 
 
-def run_area(A, frames, w, h, pad=0, out_pad=0, shift=0, src_shift=0, change=None, poison=SENTINEL, aligned=False):
+def run_area(A, frames, w, h, pad=0, out_pad=0, shift=0, src_shift=0, change=None, poison=SENTINEL, aligned=False, stream=None):
     """kbe_area_reduce_u8 on uint8 frames [n,H,W,3]: the source `src_shift` bytes off its allocation's start and its rows `pad` bytes apart
     beyond their pixels, the output's rows `out_pad`, the output `shift` bytes off its allocation's start, in a guarded allocation of its own
     per frame, every byte the poison (by default the bands' own byte).  change(args): the last word on the argument list -- a dict by the
@@ -48,7 +51,7 @@ def run_area(A, frames, w, h, pad=0, out_pad=0, shift=0, src_shift=0, change=Non
     out_stride = 3 * w + out_pad
     src, outs = _placed(guard, rows, src_shift, h * out_stride, shift, aligned)
     args = dict(frames_u8=(ctypes.c_void_p * n)(*[src.data_ptr() + i * H * (3 * W + pad) for i in range(n)]), n_frames=n, W=W, H=H, stride_bytes=3 * W + pad,
-                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), w=w, h=h, out_stride_bytes=out_stride, stream=stream())
+                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), w=w, h=h, out_stride_bytes=out_stride, stream=current_stream() if stream is None else stream)
     if change:
         change(args)
     rc = A._raw('kbe_area_reduce_u8', *args.values())
@@ -57,7 +60,7 @@ def run_area(A, frames, w, h, pad=0, out_pad=0, shift=0, src_shift=0, change=Non
     return rc, np.stack([o.cpu().numpy().reshape(h, out_stride) for o in outs])
 
 
-def run_crop_area(CA, frames, crop, size, pad=0, out_pad=0, shift=0, src_shift=0, change=None, poison=0xFF, aligned=False):
+def run_crop_area(CA, frames, crop, size, pad=0, out_pad=0, shift=0, src_shift=0, change=None, poison=0xFF, aligned=False, stream=None):
     """kbe_crop_area_u8 on uint8 frames [n,H,W,3]: the source `src_shift` bytes off its allocation's start and its rows `pad` bytes apart beyond
     their pixels, the output's rows `out_pad`, the output `shift` bytes off its allocation's start, in a guarded allocation of its own per
     frame, every byte the poison.  change(args): the last word on the argument list -- a dict by the header's names.
@@ -70,7 +73,7 @@ def run_crop_area(CA, frames, crop, size, pad=0, out_pad=0, shift=0, src_shift=0
     out_stride = 3 * w + out_pad
     src, outs = _placed(guard, rows, src_shift, h * out_stride, shift, aligned)
     args = dict(frames_u8=(ctypes.c_void_p * n)(*[src.data_ptr() + i * H * (3 * W + pad) for i in range(n)]), n_frames=n, W=W, H=H, stride_bytes=3 * W + pad, crop_w=cw, crop_h=ch,
-                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), w=w, h=h, out_stride_bytes=out_stride, stream=stream())
+                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), w=w, h=h, out_stride_bytes=out_stride, stream=current_stream() if stream is None else stream)
     if change:
         change(args)
     rc = CA._raw('kbe_crop_area_u8', *args.values())
@@ -79,7 +82,7 @@ def run_crop_area(CA, frames, crop, size, pad=0, out_pad=0, shift=0, src_shift=0
     return rc, np.stack([o.cpu().numpy().reshape(h, out_stride) for o in outs])
 
 
-def run_dof(DOF, frames, depths, focus, A, R, pad=0, z_pad=0, out_pad=0, shift=0, src_shift=0, gap=0, change=None, poison=0xFF, aligned=False):
+def run_dof(DOF, frames, depths, focus, A, R, pad=0, z_pad=0, out_pad=0, shift=0, src_shift=0, gap=0, change=None, poison=0xFF, aligned=False, stream=None):
     """kbe_dof_u8 on uint8 frames [n,H,W,3] and float32 depths [n,H,W]: the source `src_shift` bytes off its allocation's start, its rows `pad`
     bytes apart beyond their pixels and its frames `gap` bytes apart, the depth rows `z_pad` floats apart, the output's rows `out_pad` bytes,
     the output `shift` bytes off its allocation's start, in a guarded allocation of its own per frame, every byte the poison.
@@ -97,7 +100,7 @@ def run_dof(DOF, frames, depths, focus, A, R, pad=0, z_pad=0, out_pad=0, shift=0
     args = dict(frames_u8=(ctypes.c_void_p * n)(*[src.data_ptr() + i * rows.shape[1] for i in range(n)]),
                 depth_f32=(ctypes.c_void_p * n)(*[z.data_ptr() + 4 * i * H * (W + z_pad) for i in range(n)]), n_frames=n, W=W, H=H, stride_bytes=3 * W + pad,
                 depth_stride_floats=W + z_pad, focus=(ctypes.c_double * n)(*[float(f) for f in focus]), aperture=float(A), max_radius=R,
-                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), out_stride_bytes=out_stride, stream=stream())
+                out_u8=(ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), out_stride_bytes=out_stride, stream=current_stream() if stream is None else stream)
     if change:
         change(args)
     rc = DOF._raw('kbe_dof_u8', *args.values())

@@ -458,9 +458,10 @@ def test_bias_act_into_an_output_held_off_a_16_byte_boundary(K):
 # 6. glue and network kernels
 # ---------------------------------------------------------------------------------------
 
-def glue_calls(K, B, C, H, W):
-    """[(name, thunk -> tensor or tuple of tensors, exact?)]: every K. wrapper of csrc/kbe_hip.hip on inputs of one shape, made once."""
-    gen = torch.Generator().manual_seed(B * 1000 + C * 100 + H * 10 + W)
+def glue_calls(K, B, C, H, W, seed=0):
+    """[(name, thunk -> tensor or tuple of tensors, exact?)]: every K. wrapper of csrc/kbe_hip.hip on inputs of one shape, made once.
+    seed: another set of tensors of the same shapes (tests/test_streams_gpu.py: the decoy); everything that is no tensor stays what it is."""
+    gen = torch.Generator().manual_seed(B * 1000 + C * 100 + H * 10 + W + 7919 * seed)
     rnd = lambda *s: torch.randn(*s, generator=gen).cuda()
     uni = lambda *s: torch.rand(*s, generator=gen).cuda()
     N = H * W
@@ -479,9 +480,10 @@ def glue_calls(K, B, C, H, W):
     frame = (uni(H, W, 3) * 255).to(torch.uint8)
     cw, ch = max(1, W - W // 4), max(1, H - H // 4)
     cout = C + 2
-    raw, mask = rnd(B, cout, H, W), (uni(B, C, H, W) > 0.3).float()
+    keep = 0.3 if seed == 0 else 0.97       # (the decoy's masks are sparse, so that the windows without a valid pixel -- pconv_epilogue's second output -- are others)
+    raw, mask = rnd(B, cout, H, W), (uni(B, C, H, W) > keep).float()
     bias, slope, res = rnd(cout), uni(cout) * 0.5 - 0.1, rnd(B, cout, H, W)
-    slope_in, m1 = uni(C) * 0.5 - 0.1, (uni(B, 1, H, W) > 0.3).float()
+    slope_in, m1 = uni(C) * 0.5 - 0.1, (uni(B, 1, H, W) > keep).float()
     return [
         ('depth_to_points', lambda: K.depth_to_points(depth, F), True),
         ('depth_to_points valid', lambda: K.depth_to_points(depth, F, valid=valid), True),
