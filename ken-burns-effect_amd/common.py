@@ -319,7 +319,7 @@ def _prepared_cloud(K, objectCommon):
     return cached[1]
 
 
-def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_out=None, overlap=True, batch=None, out_size=None, lens=None):
+def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_out=None, overlap=True, batch=None, out_size=None, lens=None, shutter=None):
     """The frame loop proper (common.py:238-257) for a list of (focal, shift3) cameras.
 
     One fused kernel sequence per frame on the resident packed cloud; frames land in one
@@ -340,7 +340,15 @@ def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_o
     ``lens`` = dof.Lens(focus_from, focus_to, aperture, max_radius): depth of field.  The frames take a route of their own
     (_render_lens): each is rendered on its own with its float render, blurred in HBM by the depth of its pixels (dof.apply), and only
     then cropped and resized, reduced to ``out_size``, or left as it is; host_out, overlap and batch do not apply.  The sharded path does
-    not take the argument."""
+    not take the argument.
+
+    ``shutter`` = shutter.Shutter(fraction, samples): motion blur.  ``cameras`` are then the samples' cameras, ``samples`` for every frame
+    (shutter.sample_steps places them), and the frames take a route of their own (_render_shutter): the samples are rendered into HBM by
+    the routes above exactly as without a shutter -- the same crop, out_size and lens --, every frame is the mean of its finished
+    samples (shutter.mean), and only the len(cameras) / samples means are returned or fetched; host_out, overlap and batch do not apply.
+    The sharded path does not take the argument."""
+    if shutter is not None:
+        return _render_shutter(cameras, objectCommon, crop, out_size, keep_on_device, lens, shutter)
     if lens is not None:
         return _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens)
     if out_size is not None:
@@ -387,11 +395,54 @@ def _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device):
     return host.numpy()
 
 
-def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens):
+def _render_shutter(cameras, objectCommon, crop, out_size, keep_on_device, lens, shutter):
+    """render_frames(shutter=...): output frames in chunks of max(1, 96 // samples) -- at most 96 samples lie in HBM at a time, one launch of
+    the entry --, each chunk's samples rendered by the route they would take without a shutter (keep_on_device), then averaged where they lie
+    (shutter.mean).  The mean is taken on FINISHED frames, after the crop and resize or the reduction: with an out_size that is a fraction
+    of the bytes.  With a lens every sample of frame i is blurred at frame i's focus depth, dof.focus_path(from, to, n)[i]: the focus is
+    pulled between exposures, not within one."""
+    from . import shutter as shutter_of
+    shutter = shutter_of.checked(shutter)
+    S = shutter.samples
+    if len(cameras) % S or not cameras:
+        raise ValueError('render_frames(shutter=...): %d cameras are no whole number of frames of %d samples' % (len(cameras), S))
+    n = len(cameras) // S
+    chunk = max(1, 96 // S)
+    focus = None
+    if lens is not None:
+        from . import dof
+        lens = dof.checked_lens(lens)
+        focus = dof.focus_path(lens.focus_from, lens.focus_to, n)
+    out = None
+    for first in range(0, n, chunk):
+        count = min(chunk, n - first)
+        cams = cameras[first * S:(first + count) * S]
+        if lens is not None:
+            samples = _render_lens(cams, objectCommon, crop, out_size, True, lens, focus=[focus[first + k // S] for k in range(count * S)])
+        else:
+            samples = render_frames(cams, objectCommon, crop, keep_on_device=True, out_size=out_size)
+        mean = shutter_of.mean(samples, S)
+        if count == n:
+            out = mean
+        else:
+            if out is None:
+                out = torch.empty((n,) + tuple(mean.shape[1:]), dtype=torch.uint8, device=mean.device)
+            out[first:first + count].copy_(mean)
+    if keep_on_device:
+        return out
+    # (into pinned memory, once, as _render_reduced fetches its frames)
+    host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return host.numpy()
+
+
+def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens, focus=None):
     """render_frames(lens=...): groups of at most twelve frames, each frame rendered by K.render_frame with its float render (plane 3: the
     depth of every pixel, hole-filled) and no fill rectangle -- the blur reads beyond the crop's window --, the group blurred where it lies
     (dof.apply: one launch), then crop_area.reduce (out_size), K.crop_resize_u8 per frame (crop alone) or nothing more.  The focus
-    depth of frame i is dof.focus_path(focus_from, focus_to, n)[i]."""
+    depth of frame i is dof.focus_path(focus_from, focus_to, n)[i], or ``focus``[i] where the caller gives one depth per camera
+    (_render_shutter: the samples of one exposure share a depth)."""
     from . import crop_area, dof
     if out_size is not None and crop is None:
         raise ValueError('render_frames(out_size=...) reduces the crop: it needs crop=(w, h)')
@@ -403,7 +454,10 @@ def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens):
     state = _prepared_cloud(K, objectCommon)
     device = objectCommon['tensorInpaPoints'].device
     n = len(cameras)
-    focus = dof.focus_path(lens.focus_from, lens.focus_to, n)
+    if focus is None:
+        focus = dof.focus_path(lens.focus_from, lens.focus_to, n)
+    elif len(focus) != n:
+        raise ValueError('_render_lens: %d focus depths for %d cameras' % (len(focus), n))
     w, h = (W, H) if out_size is None else (int(out_size[0]), int(out_size[1]))
     out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=device)
     group = max(1, min(n, dof.FRAMES_PER_GROUP))
@@ -430,7 +484,7 @@ def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens):
     return host.numpy()
 
 
-def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False, out_size=None, lens=None):
+def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False, out_size=None, lens=None, shutter=None):
     """Renders the camera path ``dblSteps`` between two crop windows (common.py:172-263).
 
     objectSettings: dblSteps, objectFrom/objectTo {dblCenterU, dblCenterV, intCropWidth,
@@ -438,13 +492,18 @@ def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device
     Optional key ``boolCrop`` (default True): apply the crop + resize of :256-257.  ``keep_on_device``: the frames stay in HBM and
     come back as one uint8 [n,H,W,3] device tensor (for the device-side Motion-JPEG encoder).  ``out_size`` = (w, h): frames of that size,
     the crop reduced on the GPU and never enlarged (render_frames(out_size=...)); it needs the crop (``boolCrop``).  ``lens``: depth of
-    field (render_frames(lens=...))."""
+    field (render_frames(lens=...)).  ``shutter``: motion blur -- every step of ``dblSteps`` becomes ``samples`` steps around it
+    (shutter.sample_steps), rendered and averaged on the GPU (render_frames(shutter=...)); as many frames as steps come back."""
     with on_device_of(objectCommon['tensorRawPoints']):
         if 'boolInpaint' not in objectSettings or objectSettings['boolInpaint'] == True:   # noqa: E712
             build_pointcloud(objectSettings, objectCommon, moduleInpaint)
         crop = crop_size(objectSettings) if objectSettings.get('boolCrop', True) else None
+        if shutter is not None:
+            from . import shutter as shutter_of
+            shutter = shutter_of.checked(shutter)
+            objectSettings = dict(objectSettings, dblSteps=shutter_of.sample_steps(objectSettings['dblSteps'], shutter.fraction, shutter.samples))
         frames = render_frames(frame_cameras(objectSettings, objectCommon), objectCommon, crop, keep_on_device=keep_on_device, out_size=out_size,
-                               **({} if lens is None else {'lens': lens}))
+                               **({} if lens is None else {'lens': lens}), **({} if shutter is None else {'shutter': shutter}))
     if keep_on_device:
         return frames
     return [frames[i] for i in range(frames.shape[0])]

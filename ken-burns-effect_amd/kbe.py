@@ -17,6 +17,9 @@
                                                         pixels of a point at infinity, above 0; what lies at the depth of pixel U,V of the photo
                                                         stays sharp (default: the centre of the end window), and with --focus-to the focus is pulled
                                                         to that pixel's depth over the clip: env KBE_APERTURE, KBE_FOCUS, KBE_FOCUS_TO)
+        [--shutter F] [--shutter-samples S]            (new: motion blur -- the shutter is open for the share F of a frame interval, above 0 and at
+                                                        most 1, and every frame is the mean, taken on the GPU, of S frames rendered at sub-frame
+                                                        cameras on the path, S = 2..32, default 8: env KBE_SHUTTER, KBE_SHUTTER_SAMPLES)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -29,12 +32,12 @@ import numpy as np
 import torch
 
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
-                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=', 'width=', 'aperture=', 'focus=', 'focus-to=']
+                'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=', 'width=', 'aperture=', 'focus=', 'focus-to=', 'shutter=', 'shutter-samples=']
 
 
 def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
-           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None, 'width': None, 'aperture': None, 'focus': None, 'focus-to': None,
+           'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None, 'width': None, 'aperture': None, 'focus': None, 'focus-to': None, 'shutter': None, 'shutter-samples': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -73,6 +76,14 @@ def parse(argv):
             cfg['aperture'], cfg['focus'], cfg['focus-to'] = lens_request(cfg['aperture'], cfg['focus'], cfg['focus-to'])
         except ValueError as e:
             raise SystemExit('--%s' % str(e).replace('_', '-', 1) if str(e).startswith('focus') else '--aperture %s: %s' % (cfg['aperture'], e))
+    if cfg['shutter'] is not None or cfg['shutter-samples'] is not None:
+        from .pipeline import shutter_request
+        if cfg['shutter'] is None:
+            raise SystemExit('--shutter-samples %s: only with --shutter' % cfg['shutter-samples'])
+        try:
+            cfg['shutter'], cfg['shutter-samples'] = shutter_request(cfg['shutter'], cfg['shutter-samples'])
+        except ValueError as e:
+            raise SystemExit('--shutter-samples %s: %s' % (cfg['shutter-samples'], e) if 'samples' in str(e) else '--shutter %s: %s' % (cfg['shutter'], e))
     if cfg['gif-fps'] is not None:
         try:
             cfg['gif-fps'] = float(cfg['gif-fps'])
@@ -150,7 +161,8 @@ def main(argv=None):
     paths = [cfg['estim-path'], cfg['refine-path'], cfg['inpaint-path']] + ([cfg['inpaint-depth']] if cfg['inpaint-depth'] else [])
     pipe = Pipeline(model_paths=paths, dolly=cfg['dolly'], output_frames=cfg['write-frames'], pretrain=cfg['pretrained-refine'], d2=cfg['2d'],
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'],
-                    gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'])
+                    gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'],
+                    shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'])
     frames = pipe(image, zoom, cfg['out'], pretrained_estim=cfg['pretrained-estim'])
     print('%d frames of %dx%d written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], cfg['out']))
 

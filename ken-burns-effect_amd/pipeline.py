@@ -29,7 +29,7 @@ from .utils import load_models, resize_image
 
 class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
-                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None):
+                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None, shutter=None, shutter_samples=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
         # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
         # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
@@ -47,6 +47,10 @@ class Pipeline():
         # it stays); env KBE_FOCUS, KBE_FOCUS_TO as "U,V".  The depths are read from the estimated depth.  None and no env: no lens, every
         # file as before
         self.aperture, self.focus, self.focus_to = aperture, focus, focus_to
+        # shutter: motion blur -- the share of a frame interval the shutter is open, above 0 and at most 1; every frame is then the mean of
+        # shutter_samples (2..32, default 8) frames rendered at sub-frame cameras on the path around its own (shutter.py,
+        # common.render_frames(shutter=)); env KBE_SHUTTER, KBE_SHUTTER_SAMPLES.  None and no env: an instantaneous exposure, every file as before
+        self.shutter, self.shutter_samples = shutter, shutter_samples
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -171,6 +175,8 @@ class Pipeline():
         lens_at = lens_request(getattr(self, 'aperture', None), getattr(self, 'focus', None), getattr(self, 'focus_to', None))
         if lens_at is not None:
             lens_at = lens_points(lens_at, tensorImage.size(3), tensorImage.size(2), zoom_settings)
+        # KBE_SHUTTER, KBE_SHUTTER_SAMPLES (Pipeline(shutter=, shutter_samples=), kbe.py --shutter --shutter-samples): before any network runs too
+        open_for = shutter_request(getattr(self, 'shutter', None), getattr(self, 'shutter_samples', None))
         with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
             self.estimate(tensorImage)
             if inpaint_depth:
@@ -192,7 +198,8 @@ class Pipeline():
             frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                               'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                               'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device,
-                                             **({} if out_size is None else {'out_size': out_size}), **lens)     # (without a width or a lens the call is what it was)
+                                             **({} if out_size is None else {'out_size': out_size}), **lens,
+                                             **({} if open_for is None else {'shutter': open_for}))     # (without a width, a lens or a shutter the call is what it was)
         if on_device:
             os.makedirs(output_path, exist_ok=True)
             # (the frames are in the INPUT's channel order, as below: the encoders read B, G, R unless --pretrained-estim)
@@ -399,6 +406,35 @@ def lens_request(aperture=None, focus=None, focus_to=None):
     if not (math.isfinite(aperture) and aperture > 0.0):
         raise ValueError('the aperture (KBE_APERTURE, --aperture): pixels, a finite number above 0')
     return aperture, None if focus is None else _focus_point(focus, 'focus'), None if focus_to is None else _focus_point(focus_to, 'focus_to')
+
+
+def shutter_request(shutter=None, samples=None):
+    """shutter.Shutter(fraction, samples), or None for an instantaneous exposure: what Pipeline was told, else env KBE_SHUTTER,
+    KBE_SHUTTER_SAMPLES (kbe.py --shutter, --shutter-samples).  The fraction is finite, above 0 and at most 1; the samples are an integer 2..32,
+    8 where none is given; samples without a shutter are refused."""
+    from .shutter import MAX_SAMPLES, Shutter
+    shutter = shutter if shutter is not None else os.environ.get('KBE_SHUTTER') or None
+    samples = samples if samples is not None else os.environ.get('KBE_SHUTTER_SAMPLES') or None
+    if shutter is None:
+        if samples is not None:
+            raise ValueError('shutter_samples (KBE_SHUTTER_SAMPLES, --shutter-samples): only with a shutter (KBE_SHUTTER, --shutter)')
+        return None
+    try:
+        shutter = float(shutter)
+    except (TypeError, ValueError):
+        shutter = 0.0
+    if not (math.isfinite(shutter) and 0.0 < shutter <= 1.0):
+        raise ValueError('the shutter (KBE_SHUTTER, --shutter): the share of a frame interval it is open, a finite number above 0 and at most 1')
+    if samples is None:
+        return Shutter(shutter)
+    try:
+        whole = int(samples)
+        samples = whole if whole == float(samples) and not isinstance(samples, bool) else 0
+    except (TypeError, ValueError, OverflowError):
+        samples = 0
+    if not 2 <= samples <= MAX_SAMPLES:
+        raise ValueError('the shutter\'s samples (KBE_SHUTTER_SAMPLES, --shutter-samples): a whole number, 2..%d' % MAX_SAMPLES)
+    return Shutter(shutter, samples)
 
 
 def lens_points(request, W, H, zoom_settings):
