@@ -29,7 +29,7 @@ from .utils import load_models, resize_image
 
 class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
-                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None, shutter=None, shutter_samples=None):
+                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None, shutter=None, shutter_samples=None, y4m=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
         # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
         # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
@@ -51,6 +51,9 @@ class Pipeline():
         # shutter_samples (2..32, default 8) frames rendered at sub-frame cameras on the path around its own (shutter.py,
         # common.render_frames(shutter=)); env KBE_SHUTTER, KBE_SHUTTER_SAMPLES.  None and no env: an instantaneous exposure, every file as before
         self.shutter, self.shutter_samples = shutter, shutter_samples
+        # y4m: also write 3d_kbe.y4m beside the video -- the clip as planar Y'CbCr 4:2:0 in a YUV4MPEG2 file, the one uncompressed format that
+        # video encoders and players read, converted on the GPU (yuv.py); None: env KBE_Y4M=1.  Opt-in: without it every file is written as before
+        self.y4m = y4m
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -160,6 +163,8 @@ class Pipeline():
             gif_wide, gif_every = gif_shape(getattr(self, 'gif_width', None), getattr(self, 'gif_fps', None))
             if gif_wide is not None and gif_wide > tensorImage.size(3):
                 raise ValueError('a GIF %d pixels wide from an image %d wide: the GIF is only ever reduced' % (gif_wide, tensorImage.size(3)))
+        # KBE_Y4M=1 (Pipeline(y4m=True), kbe.py --y4m): the frames stay in HBM as with the GIF, and 3d_kbe.y4m is converted from them (yuv.py)
+        y4m_on = output_path is not None and y4m_switch(getattr(self, 'y4m', None))
         # KBE_WIDTH (Pipeline(width=), kbe.py --width): looked at before any network runs as well
         wide = out_width(getattr(self, 'width', None))
         out_size = None
@@ -189,7 +194,7 @@ class Pipeline():
             jpeg_on_device = output_path is not None and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
             png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
             video_from_hbm = jpeg_on_device and (png_on_device or not self.output_frames)
-            on_device = png_on_device or video_from_hbm or gif_on
+            on_device = png_on_device or video_from_hbm or gif_on or y4m_on
             lens = {}
             if lens_at is not None:
                 from . import dof
@@ -211,13 +216,16 @@ class Pipeline():
                 gif_size = None if gif_wide is None else area.size_for(frames.shape[2], frames.shape[1], width=gif_wide)
                 gif.write_gif(os.path.join(output_path, '3d_kbe.gif'), frames, fps=25, bgr=not pretrained_estim, dither=gif_dither(getattr(self, 'gif_dither', None)),
                               size=gif_size, every=gif_every)
+            if y4m_on:
+                from . import yuv
+                yuv.write_y4m(os.path.join(output_path, '3d_kbe.y4m'), frames, fps=25, bgr=not pretrained_estim)
             if video_from_hbm:
                 encoded = jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=not pretrained_estim)
                 # forth and back (:131): every distinct frame was encoded once, the way back is the same byte objects again
                 write_video(os.path.join(output_path, '3d_kbe.mp4'), None, fps=25, jpegs=encoded + encoded[-2::-1], frame_size=tuple(frames.shape[1:3]))
             host = frames.cpu().numpy()                                                 # the return value (with video_from_hbm: fetched after the video is written)
             out = [host[i] for i in range(host.shape[0])]
-            png_on_host = bool(self.output_frames) and not png_on_device               # (only with the GIF: the PNG frames from the fetched frames, as without it)
+            png_on_host = bool(self.output_frames) and not png_on_device               # (only with the GIF or the y4m file: the PNG frames from the fetched frames, as without it)
             if png_on_host or not video_from_hbm:
                 rgb = out if pretrained_estim else [f[:, :, ::-1] for f in out]
                 if png_on_host:
@@ -314,6 +322,11 @@ def png_encoder():
 def gif_switch(gif=None):
     """Whether 3d_kbe.gif is written beside the video: what Pipeline was told, else env KBE_GIF=1 (kbe.py --gif).  Off by default."""
     return bool(gif) if gif is not None else os.environ.get('KBE_GIF', '0') == '1'
+
+
+def y4m_switch(y4m=None):
+    """Whether 3d_kbe.y4m is written beside the video: what Pipeline was told, else env KBE_Y4M=1 (kbe.py --y4m).  Off by default."""
+    return bool(y4m) if y4m is not None else os.environ.get('KBE_Y4M', '0') == '1'
 
 
 def gif_dither(kind=None):
