@@ -256,6 +256,41 @@ KBO_API void kbo_accumulate(const float* points, const float* data, int B, int N
     }
 }
 
+/* kbo_accumulate with exact sums: the same projection, fp32 corner weights, inside and z tests, but
+   sum[B,C+1,H,W] (double, zero-filled by the caller) accumulates (double) data * (double) w -- the product of
+   two fp32 values is exact in fp64 -- and (double) w; count[B,H,W] (int, zero-filled) the contributions per
+   pixel.  Not a restatement of the reference: what ANY legal order of its fp32 sums is held against
+   (tests/interval_cases.py).  drop_wsum (NULL: none; else [B,H,W], a first pass's weight sums) makes the MUTANT
+   the tests show the interval against: contributions below drop_below of their pixel's weight sum are lost.  fp64 sums of at most a few dozen non-negative terms carry a relative error
+   below n * 2^-53, nine orders of magnitude under the fp32 interval. */
+KBO_API void kbo_accumulate_f64(const float* points, const float* data, int B, int N, int C,
+                                const float* zee, int W, int H, double focal, double baseline,
+                                int use_fma, const double* drop_wsum, double drop_below, double* sum, int32_t* count)
+{
+    const size_t HW = (size_t) H * W;
+    for (int b = 0; b < B; b++) {
+        const float* P = points + (size_t) b * 3 * N;
+        const float* D = data + (size_t) b * C * N;
+        const float* Z = zee + (size_t) b * HW;
+        double* A = sum + (size_t) b * (C + 1) * HW;
+        int32_t* K = count + (size_t) b * HW;
+        for (int i = 0; i < N; i++) {
+            kbo_proj p;
+            if (!kbo_project(P[i], P[N + i], P[2 * (size_t) N + i], focal, baseline, W, H, use_fma, &p)) continue;
+            for (int c = 0; c < 4; c++) {
+                if (!kbo_inside(p.x[c], p.y[c], W, H)) continue;                /* :638 */
+                const size_t px = (size_t) p.y[c] * W + p.x[c];
+                if (!((double) p.err <= (double) Z[px] + 1.0)) continue;         /* :639 */
+                if (drop_wsum && (double) p.w[c] < drop_below * drop_wsum[(size_t) b * HW + px]) continue;     /* the mutant */
+                for (int ch = 0; ch < C; ch++)
+                    A[ch * HW + px] += (double) D[(size_t) ch * N + i] * (double) p.w[c];
+                A[C * HW + px] += (double) p.w[c];
+                K[px] += 1;
+            }
+        }
+    }
+}
+
 /* common.py:686  output[:, :-1] / (output[:, -1:] + 0.0000001), output[:, -1:].clone() */
 KBO_API void kbo_normalize(const float* acc, int B, int C, int W, int H, float* render, float* existing)
 {

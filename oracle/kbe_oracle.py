@@ -34,7 +34,7 @@ def lib():
         build()
         _lib = ctypes.CDLL(_SO)
         for name in ('kbo_zsplat', 'kbo_fill_zee', 'kbo_degrid_serial', 'kbo_degrid_jacobi', 'kbo_accumulate',
-                     'kbo_normalize', 'kbo_fill_disocclusion', 'kbo_depth_to_points', 'kbo_shift_points',
+                     'kbo_accumulate_f64', 'kbo_normalize', 'kbo_fill_disocclusion', 'kbo_depth_to_points', 'kbo_shift_points',
                      'kbo_laplacian', 'kbo_median', 'kbo_frame_u8', 'kbo_pconv_epilogue', 'kbo_generate_mask'):
             getattr(_lib, name).restype = None
     return _lib
@@ -111,6 +111,24 @@ def accumulate(points, data, zee, focal, baseline, use_fma=True):
     lib().kbo_accumulate(_p(points), _p(data), _i(B), _i(N), _i(C), _p(_f32(zee)), _i(W), _i(H),
                          _d(float(focal)), _d(float(baseline)), _i(int(use_fma)), _p(acc))
     return acc
+
+
+def accumulate_exact(points, data, zee, focal, baseline, use_fma=True, drop_below=None):
+    """kbo_accumulate with exact (fp64) sums on the z-buffer `zee` -> (mean64 [B,C,H,W], wsum64 [B,1,H,W], both float64, and
+    n [B,1,H,W] int32, the number of contributions of each pixel).  mean64 = S / (wsum64 + (double) 1e-7f): the exact value of what
+    accumulate + normalize round; tests/interval_cases.py derives the interval every fp32 evaluation of it lies in.
+    drop_below = (wsum64 of a first pass, share): the mutant that loses every contribution below that share of its pixel's weight sum."""
+    points, data = _f32(points), _f32(data)
+    B, C, N = data.shape
+    _, _, H, W = zee.shape
+    acc = torch.zeros(B, C + 1, H, W, dtype=torch.float64)
+    n = torch.zeros(B, 1, H, W, dtype=torch.int32)
+    drop_wsum, share = (None, 0.0) if drop_below is None else (drop_below[0].detach().to(torch.float64).contiguous(), float(drop_below[1]))
+    assert drop_wsum is None or drop_wsum.numel() == B * H * W
+    lib().kbo_accumulate_f64(_p(points), _p(data), _i(B), _i(N), _i(C), _p(_f32(zee)), _i(W), _i(H),
+                             _d(float(focal)), _d(float(baseline)), _i(int(use_fma)), _p(drop_wsum), _d(share), _p(acc), _p(n))
+    wsum = acc[:, C:].clone()
+    return acc[:, :C] / (wsum + float(np.float32(0.0000001))), wsum, n
 
 
 def normalize(acc):
