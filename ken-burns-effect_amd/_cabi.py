@@ -6,7 +6,7 @@ import ctypes
 import os
 import re
 
-_BY_VALUE = {'int': ctypes.c_int, 'size_t': ctypes.c_size_t, 'double': ctypes.c_double, 'float': ctypes.c_float, 'kbe_stream_t': ctypes.c_void_p}
+_BY_VALUE = {'int': ctypes.c_int, 'size_t': ctypes.c_size_t, 'double': ctypes.c_double, 'float': ctypes.c_float, 'uint32_t': ctypes.c_uint32, 'kbe_stream_t': ctypes.c_void_p}
 
 
 def _ctype(decl, name, returned=False):

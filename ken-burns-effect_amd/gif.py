@@ -162,12 +162,13 @@ def kept_frames(n, every):
     return kept if kept[-1] == n - 1 else kept + [n - 1]
 
 
-def write_gif(path, frames_in_hbm, fps=25, bgr=False, dither='ordered', *, size=None, every=1):
+def write_gif(path, frames_in_hbm, fps=25, bgr=False, dither='ordered', *, size=None, every=1, back=True):
     """The frames, forth and back, as an animated GIF that loops for ever: one palette for the whole clip from the frames' histogram,
     every distinct frame encoded once -- a unit holds no field that depends on its place, the way back is the same byte objects again.
     ``size``: (w, h), neither above the frames' -- the frames are reduced on the device first (area.reduce: the exact area average; see
     area.size_for), palette and all come from the reduced frames.  ``every``: only the frames of kept_frames are written, each shown
-    delay_for(fps / every) long.  Without the two the file is what it was before they existed.
+    delay_for(fps / every) long.  Without the two the file is what it was before they existed.  ``back``: False for a clip that plays forth
+    only (a slideshow): every frame once.
     -> (the palette, the number of frames in the file)"""
     if every != 1:
         import torch
@@ -180,7 +181,8 @@ def write_gif(path, frames_in_hbm, fps=25, bgr=False, dither='ordered', *, size=
     H, W = int(frames_in_hbm.shape[1]), int(frames_in_hbm.shape[2])
     palette = palette_from_histogram(histogram(frames_in_hbm, bgr=bgr))
     units = encode(frames_in_hbm, lut(palette), bgr=bgr, dither=dither, delay_cs=delay_for(fps))
-    units = units + units[-2::-1]
+    if back:
+        units = units + units[-2::-1]
     with open(path, 'wb') as f:
         f.write(assemble(units, W, H, palette))
     return palette, len(units)

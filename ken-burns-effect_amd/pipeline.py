@@ -147,6 +147,39 @@ class Pipeline():
         with common.on_device_of(getattr(self, 'device', torch.device('cpu'))):      # the C ABI launches on the current device's stream
             return self._run(tensorImage, zoom_settings, output_path, inpaint_depth, pretrained_estim)
 
+    @torch.no_grad()
+    def render(self, tensorImage, zoom_settings):
+        """The clip's frames as a uint8 [steps,H,W,3] tensor in HBM, and nothing written: what _run renders, with the instance's width, lens
+        and shutter, up to process_kenburns(keep_on_device=True).  For callers that go on with the frames on the device (slideshow.py).  _run is kept
+        byte for byte what it was, so its first half is repeated here: an option that _run learns has to be taught to this method as well
+        (tests/test_transition_gpu.py holds the two to the same process_kenburns call)."""
+        from .utils import miopen_tuned_once
+        with common.on_device_of(getattr(self, 'device', torch.device('cpu'))):
+            auto = getattr(self, 'miopen_find', False) == 'auto'
+            wide = out_width(getattr(self, 'width', None))
+            out_size = None
+            if wide is not None:
+                try:
+                    out_size = width_size(wide, tensorImage.size(3), tensorImage.size(2), zoom_settings)
+                except ValueError as e:
+                    raise ValueError('width %d: %s' % (wide, e)) from None
+            lens_at = lens_request(getattr(self, 'aperture', None), getattr(self, 'focus', None), getattr(self, 'focus_to', None))
+            if lens_at is not None:
+                lens_at = lens_points(lens_at, tensorImage.size(3), tensorImage.size(2), zoom_settings)
+            open_for = shutter_request(getattr(self, 'shutter', None), getattr(self, 'shutter_samples', None))
+            with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
+                self.estimate(tensorImage)
+                lens = {}
+                if lens_at is not None:
+                    from . import dof
+                    aperture, near, far = lens_at
+                    lens = {'lens': dof.Lens(dof.focus_depth(self.objectCommon['tensorRawDepth'], *near), dof.focus_depth(self.objectCommon['tensorRawDepth'], *far), aperture)}
+                return common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
+                                                'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
+                                                'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=True,
+                                               **({} if out_size is None else {'out_size': out_size}), **lens,
+                                               **({} if open_for is None else {'shutter': open_for}))
+
     def tuning_tag(self, width, height):
         """What MIOpen is tuned for, once per machine (utils.miopen_tuned_once): this pipeline's networks at this image size."""
         return '%dx%d-%s%s%s' % (width, height, 'partial' if self.partial_inpainting else 'plain', '-dolly' if self.dolly else '',

@@ -1,0 +1,217 @@
+"""Slideshows: several photos in one video, every photo a Ken Burns clip, the clips joined on the GPU by transitions (transition.py):
+
+    python -m ken_burns_effect_amd.slideshow --in a.jpg --in b.jpg [--in c.jpg ...] --out outdir
+        [--transition dissolve|wipe-right|wipe-left|wipe-down|wipe-up|fade]   (default dissolve)
+        [--transition-frames T]                        (default 12: the last T frames of a clip and the first T of the next become T frames)
+        [--softness S]                                 (the wipes' soft edge in pixels, 1..65535; default: an eighth of the wipe's extent, at least 1)
+        [--fade-colour R,G,B]                          (the colour the fade, --fade-in and --fade-out go through; default 0,0,0)
+        [--fade-in N] [--fade-out N]                   (the show's first / last N frames come from / go to the colour; default 0)
+        and of kbe.py's options: [--dolly] [--width N] [--aperture A] [--focus U,V] [--focus-to U,V] [--shutter F] [--shutter-samples S]
+        [--gif] [--gif-dither none|ordered] [--gif-width N] [--gif-fps F] [--y4m] [--write-frames] [--jpeg native|pillow|device]
+        [--png native|device] [--inpaint-path P] [--refine-path P] [--estim-path P] [--inpaint-depth P] [--pretrained-refine]
+        [--pretrained-estim] [--2d] [--semantics-path P] [--allow-random-weights]
+
+One Pipeline is built: the networks are loaded once.  Every photo gets kbe.py's default windows (window options are not taken) and its clip
+plays forth only; Pipeline.render leaves each clip's frames in HBM, transition.join makes one tensor of them, and the writers take the
+frames where they lie: slideshow.mp4 -- encoded on the GPU under KBE_JPEG=device where there is no ffmpeg binary, otherwise the frames are
+fetched once for write_video --, and with the switches slideshow.gif, slideshow.y4m and frames/*.png.  All photos must give frames of one
+size: the image's, or --width's.
+"""
+import getopt
+import os
+import shutil
+import sys
+
+import torch
+
+from . import kbe, transition
+
+STEPS = 75                # the frames of every clip on the command line (Pipeline's default)
+OWN_OPTIONS = ['transition=', 'transition-frames=', 'softness=', 'fade-colour=', 'fade-in=', 'fade-out=']
+WINDOW_OPTIONS = ('startU=', 'startV=', 'endU=', 'endV=', 'startW=', 'startH=', 'endW=', 'endH=')
+LONG_OPTIONS = [o for o in kbe.LONG_OPTIONS if o not in WINDOW_OPTIONS] + OWN_OPTIONS
+NO_WINDOW = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
+
+
+def _whole(text):
+    """A whole number 0 or more from the command line's text or a number, or None."""
+    if isinstance(text, int) and not isinstance(text, bool):
+        return text if text >= 0 else None
+    return int(text) if isinstance(text, str) and text.isdigit() else None
+
+
+def colour_bytes(text):
+    """(R, G, B) from "R,G,B" or three numbers, 0..255 each, or ValueError."""
+    try:
+        parts = text.split(',') if isinstance(text, str) else list(text)
+        values = [_whole(v.strip() if isinstance(v, str) else v) for v in parts]
+    except (TypeError, AttributeError):
+        values = []
+    if len(values) != 3 or any(v is None or v > 255 for v in values):
+        raise ValueError('the fade colour (--fade-colour): R,G,B, three whole numbers 0..255')
+    return tuple(values)
+
+
+def frame_size(W, H, zoom, width=None):
+    """(w, h) of the frames a W x H photo gives under these windows: the photo's size, or --width's (pipeline.width_size)."""
+    from .pipeline import width_size
+    return (int(W), int(H)) if width is None else width_size(width, W, H, zoom)
+
+
+def checked(sizes, steps, transition_kind='dissolve', transition_frames=12, softness=None, fade_colour=(0, 0, 0), fade_in=0, fade_out=0, width=None, dolly=False, names=None):
+    """What a slideshow of photos of these (W, H) sizes will be, from the sizes, the default windows and the width alone -- before any network runs:
+    {'size': (w, h) of every frame, 'zooms', 'kind', 'T', 'softness', 'colour': (R, G, B), 'fade_in', 'fade_out', 'plan': transition.join_plan's}, or ValueError
+    whose text begins with the option at fault."""
+    names = list(names) if names is not None else ['photo %d' % i for i in range(len(sizes))]
+    if len(sizes) < 1:
+        raise ValueError('--in: a slideshow takes one photo or more')
+    if transition_kind not in transition.KINDS:
+        raise ValueError('--transition %s: %s' % (transition_kind, ', '.join(transition.KINDS)))
+    T, steps = _whole(transition_frames), int(steps)
+    if len(sizes) > 1 and not (T is not None and 1 <= T <= steps // 2):
+        raise ValueError("--transition-frames %s: 1..%d, half of a clip's %d frames" % (transition_frames, steps // 2, steps))
+    if softness is not None and not (_whole(softness) is not None and 1 <= _whole(softness) <= transition.MAX_SOFTNESS):
+        raise ValueError("--softness %s: the wipes' soft edge in pixels, 1..%d" % (softness, transition.MAX_SOFTNESS))
+    try:
+        colour = colour_bytes(fade_colour)
+    except ValueError as e:
+        raise ValueError('--fade-colour %s: %s' % (fade_colour if isinstance(fade_colour, str) else (fade_colour,), e)) from None
+    used = T if len(sizes) > 1 else 0
+    for option, value in (('--fade-in', fade_in), ('--fade-out', fade_out)):
+        if _whole(value) is None or _whole(value) > steps - used:
+            raise ValueError("%s %s: 0..%d, the frames of a clip of %d that no transition uses" % (option, value, steps - used, steps))
+    if len(sizes) == 1 and _whole(fade_in) + _whole(fade_out) > steps:
+        raise ValueError("--fade-out %s: with --fade-in %s more than the clip's %d frames" % (fade_out, fade_in, steps))
+    zooms, size = [], None
+    for i, (W, H) in enumerate(sizes):
+        zooms.append(kbe.windows_for(W, H, NO_WINDOW, dolly))
+        try:
+            mine = frame_size(W, H, zooms[-1], width)
+        except ValueError as e:
+            raise ValueError('--width %d: %s: %s' % (width, names[i], e)) from None
+        if size is None:
+            size = mine
+        elif mine != size:
+            raise ValueError("--in %s: its frames are %dx%d and %s's are %dx%d: a slideshow's photos give frames of one size (see --width)" % (
+                names[i], mine[0], mine[1], names[0], size[0], size[1]))
+    kind = transition.KINDS[transition_kind]
+    return {'size': size, 'zooms': zooms, 'kind': kind, 'T': used, 'colour': colour, 'fade_in': _whole(fade_in), 'fade_out': _whole(fade_out),
+            'softness': _whole(softness) if softness is not None else transition.default_softness(kind, size[0], size[1]),
+            'plan': transition.join_plan([steps] * len(sizes), used, _whole(fade_in), _whole(fade_out))}
+
+
+def parse(argv):
+    """(cfg of kbe.parse with 'in' a list of paths and the slideshow's own options) from the command line, or SystemExit."""
+    try:
+        options = getopt.getopt(argv, '', LONG_OPTIONS)[0]
+    except getopt.GetoptError as e:
+        raise SystemExit('%s%s' % (e, ': window options are not taken, every photo gets the default windows' if str(e.opt) + '=' in WINDOW_OPTIONS else ''))
+    own = {'transition': 'dissolve', 'transition-frames': '12', 'softness': None, 'fade-colour': '0,0,0', 'fade-in': '0', 'fade-out': '0'}
+    images, rest = [], []
+    for option, argument in options:
+        name = option[2:]
+        if name == 'in':
+            images.append(argument)
+        elif name in own:
+            own[name] = argument
+        else:
+            rest += [option] + ([argument] if name + '=' in LONG_OPTIONS else [])
+    cfg = kbe.parse(rest)[0]
+    cfg.update(own)
+    cfg['in'] = images
+    if cfg['out'] == 'images/kbe':
+        cfg['out'] = 'images/slideshow'
+    return cfg
+
+
+def make(images, out_dir, pipe, transition_kind='dissolve', transition_frames=12, softness=None, fade_colour=(0, 0, 0), fade_in=0, fade_out=0,
+         pretrained_estim=False, gif=False, y4m=False, names=None):
+    """images: [1,3,H,W] tensors in 0..1, one per photo -> the slideshow's frames as a list of uint8 arrays, written to out_dir (None: nothing
+    is written) as slideshow.mp4 and, with gif / y4m / pipe.output_frames, slideshow.gif, slideshow.y4m and frames/*.png.  pipe: the one
+    Pipeline whose render makes every clip, pipe.steps frames each, with its width, lens and shutter.  ValueError (checked) before a network runs."""
+    from . import pipeline as P
+    width = P.out_width(getattr(pipe, 'width', None))
+    show = checked([(int(t.shape[3]), int(t.shape[2])) for t in images], pipe.steps, transition_kind, transition_frames, softness, fade_colour, fade_in, fade_out,
+                   width=width, dolly=bool(pipe.dolly), names=names)
+    gif_on = out_dir is not None and bool(gif)
+    if gif_on:
+        gif_wide, gif_every = P.gif_shape(getattr(pipe, 'gif_width', None), getattr(pipe, 'gif_fps', None))
+        if gif_wide is not None and gif_wide > show['size'][0]:
+            raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif_wide, show['size'][0]))
+    R, G, B = show['colour']
+    bgr = not pretrained_estim                                      # (the frames are in the INPUT's channel order: B, G, R unless --pretrained-estim)
+    clips = [pipe.render(image, zoom) for image, zoom in zip(images, show['zooms'])]
+    with P.common.on_device_of(pipe.device):
+        frames = transition.join(clips, show['kind'], show['T'], show['softness'], (B, G, R) if bgr else (R, G, B), show['fade_in'], show['fade_out'])
+        del clips
+        if out_dir is None:
+            host = frames.cpu().numpy()
+            return [host[i] for i in range(host.shape[0])]
+        os.makedirs(out_dir, exist_ok=True)
+        png_on = bool(pipe.output_frames)
+        if png_on and P.png_encoder() == 'device':
+            from . import _native
+            P.write_frames(os.path.join(out_dir, 'frames'), None, pngs=_native.kernels().png_encode(frames, bgr=bgr))
+            png_on = False
+        if gif_on:
+            from . import area, gif as G_
+            size = None if gif_wide is None else area.size_for(frames.shape[2], frames.shape[1], width=gif_wide)
+            G_.write_gif(os.path.join(out_dir, 'slideshow.gif'), frames, fps=25, bgr=bgr, dither=P.gif_dither(getattr(pipe, 'gif_dither', None)), size=size, every=gif_every, back=False)
+        if y4m:
+            from . import yuv
+            yuv.write_y4m(os.path.join(out_dir, 'slideshow.y4m'), frames, fps=25, bgr=bgr, back=False)
+        video_from_hbm = shutil.which('ffmpeg') is None and P.jpeg_encoder()[0] == 'device'
+        if video_from_hbm:
+            P.write_video(os.path.join(out_dir, 'slideshow.mp4'), None, fps=25, jpegs=P.jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=bgr), frame_size=tuple(frames.shape[1:3]))
+        host = frames.cpu().numpy()                                 # fetched once
+    out = [host[i] for i in range(host.shape[0])]
+    if png_on or not video_from_hbm:
+        rgb = [f[:, :, ::-1] for f in out] if bgr else out
+        if png_on:
+            P.write_frames(os.path.join(out_dir, 'frames'), rgb)
+        if not video_from_hbm:
+            P.write_video(os.path.join(out_dir, 'slideshow.mp4'), rgb, fps=25)
+    return out
+
+
+def main(argv=None):
+    from .pipeline import Pipeline
+    torch.set_grad_enabled(False)
+    cfg = parse(sys.argv[1:] if argv is None else argv)
+    if cfg['jpeg'] is not None:
+        if cfg['jpeg'] not in ('native', 'pillow', 'device'):
+            raise SystemExit('--jpeg %s: native, pillow or device' % cfg['jpeg'])
+        os.environ['KBE_JPEG'] = cfg['jpeg']
+    if cfg['png'] is not None:
+        os.environ['KBE_PNG'] = cfg['png']
+    if not cfg['in']:
+        raise SystemExit('--in: a slideshow takes one photo or more')
+    if cfg['transition'] not in transition.KINDS:                       # (before a file is read)
+        raise SystemExit('--transition %s: %s' % (cfg['transition'], ', '.join(transition.KINDS)))
+    images = [kbe.load_image(path, cfg['pretrained-estim']) for path in cfg['in']]
+    settings = dict(transition_kind=cfg['transition'], transition_frames=cfg['transition-frames'], softness=cfg['softness'], fade_colour=cfg['fade-colour'],
+                    fade_in=cfg['fade-in'], fade_out=cfg['fade-out'])
+    try:                                                                # (before any network is built)
+        show = checked([(int(t.shape[3]), int(t.shape[2])) for t in images], STEPS, width=cfg['width'], dolly=cfg['dolly'], names=cfg['in'], **settings)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if cfg['gif-width'] is not None and cfg['gif-width'] > show['size'][0]:
+        raise SystemExit('--gif-width %d: the frames are %d pixels wide, and the GIF is only ever reduced' % (cfg['gif-width'], show['size'][0]))
+    if cfg['aperture'] is not None:
+        from .pipeline import lens_points
+        for image, zoom, path in zip(images, show['zooms'], cfg['in']):
+            try:
+                lens_points((cfg['aperture'], cfg['focus'], cfg['focus-to']), image.shape[3], image.shape[2], zoom)
+            except ValueError as e:
+                raise SystemExit('--%s (%s)' % (str(e).replace('_', '-', 1), path))
+    paths = [cfg['estim-path'], cfg['refine-path'], cfg['inpaint-path']] + ([cfg['inpaint-depth']] if cfg['inpaint-depth'] else [])
+    pipe = Pipeline(model_paths=paths, dolly=cfg['dolly'], output_frames=cfg['write-frames'], pretrain=cfg['pretrained-refine'], d2=cfg['2d'],
+                    semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif_dither=cfg['gif-dither'],
+                    gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'],
+                    shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'], steps=STEPS)
+    frames = make(images, cfg['out'], pipe, pretrained_estim=cfg['pretrained-estim'], gif=cfg['gif'], y4m=cfg['y4m'], names=cfg['in'], **settings)
+    print('%d frames of %dx%d from %d photos written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], len(images), cfg['out']))
+
+
+if __name__ == '__main__':
+    main()
