@@ -29,7 +29,8 @@ from .utils import load_models, resize_image
 
 class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
-                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None, shutter=None, shutter_samples=None, y4m=None):
+                 device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None, shutter=None, shutter_samples=None, y4m=None,
+                 overlay=None, overlay_at=None, overlay_opacity=None, caption=None, caption_at=None, caption_size=None, font=None, overlay_margin=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
         # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
         # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
@@ -54,6 +55,15 @@ class Pipeline():
         # y4m: also write 3d_kbe.y4m beside the video -- the clip as planar Y'CbCr 4:2:0 in a YUV4MPEG2 file, the one uncompressed format that
         # video encoders and players read, converted on the GPU (yuv.py); None: env KBE_Y4M=1.  Opt-in: without it every file is written as before
         self.y4m = y4m
+        # overlay: the path of a picture file composited onto every frame where the frames lie, in HBM -- a watermark (overlay.py); overlay_at: one
+        # of overlay.ANCHORS or "X,Y" (default bottom-right); overlay_opacity: above 0 and at most 1 (default 1).  caption: a text drawn on a
+        # plate and composited the same way, under the watermark; caption_at (default bottom); caption_size: the font's pixels (default
+        # max(12, frame height // 18)); font: the path of a TrueType file (default: Pillow's built-in face).  overlay_margin: the distance of
+        # both from the edges their anchors name (default max(4, frame width // 32)).  All in frame coordinates, after `width`.  env
+        # KBE_OVERLAY, KBE_OVERLAY_AT, KBE_OVERLAY_OPACITY, KBE_CAPTION, KBE_CAPTION_AT, KBE_CAPTION_SIZE.  None and no env: no layer, every
+        # file as before
+        self.overlay, self.overlay_at, self.overlay_opacity, self.overlay_margin = overlay, overlay_at, overlay_opacity, overlay_margin
+        self.caption, self.caption_at, self.caption_size, self.font = caption, caption_at, caption_size, font
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -167,6 +177,8 @@ class Pipeline():
             if lens_at is not None:
                 lens_at = lens_points(lens_at, tensorImage.size(3), tensorImage.size(2), zoom_settings)
             open_for = shutter_request(getattr(self, 'shutter', None), getattr(self, 'shutter_samples', None))
+            # (the layers' colour bytes in the frames' order: B, G, R, unless the caller fed R, G, B and says so in self.overlay_bgr)
+            layers = layers_of(self, out_size or (lambda: (tensorImage.size(3), tensorImage.size(2))), bgr=getattr(self, 'overlay_bgr', True))
             with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
                 self.estimate(tensorImage)
                 lens = {}
@@ -174,11 +186,11 @@ class Pipeline():
                     from . import dof
                     aperture, near, far = lens_at
                     lens = {'lens': dof.Lens(dof.focus_depth(self.objectCommon['tensorRawDepth'], *near), dof.focus_depth(self.objectCommon['tensorRawDepth'], *far), aperture)}
-                return common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
+                return with_layers(layers, common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                                 'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                                 'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=True,
                                                **({} if out_size is None else {'out_size': out_size}), **lens,
-                                               **({} if open_for is None else {'shutter': open_for}))
+                                               **({} if open_for is None else {'shutter': open_for})))
 
     def tuning_tag(self, width, height):
         """What MIOpen is tuned for, once per machine (utils.miopen_tuned_once): this pipeline's networks at this image size."""
@@ -215,6 +227,9 @@ class Pipeline():
             lens_at = lens_points(lens_at, tensorImage.size(3), tensorImage.size(2), zoom_settings)
         # KBE_SHUTTER, KBE_SHUTTER_SAMPLES (Pipeline(shutter=, shutter_samples=), kbe.py --shutter --shutter-samples): before any network runs too
         open_for = shutter_request(getattr(self, 'shutter', None), getattr(self, 'shutter_samples', None))
+        # KBE_OVERLAY, KBE_CAPTION and their kin (Pipeline(overlay=, caption=, ...), kbe.py --overlay --caption): the file is read and the caption
+        # drawn before any network runs too, for frames of the size they will have; the frames then stay in HBM, where the layers are composited
+        layers = layers_of(self, out_size or (lambda: (tensorImage.size(3), tensorImage.size(2))), bgr=not pretrained_estim)
         with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
             self.estimate(tensorImage)
             if inpaint_depth:
@@ -227,7 +242,7 @@ class Pipeline():
             jpeg_on_device = output_path is not None and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
             png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
             video_from_hbm = jpeg_on_device and (png_on_device or not self.output_frames)
-            on_device = png_on_device or video_from_hbm or gif_on or y4m_on
+            on_device = png_on_device or video_from_hbm or gif_on or y4m_on or bool(layers)
             lens = {}
             if lens_at is not None:
                 from . import dof
@@ -239,6 +254,10 @@ class Pipeline():
                                              **({} if out_size is None else {'out_size': out_size}), **lens,
                                              **({} if open_for is None else {'shutter': open_for}))     # (without a width, a lens or a shutter the call is what it was)
         if on_device:
+            with_layers(layers, frames)                                                 # the caption, then the watermark: in place, before every output
+            if output_path is None:                                                     # (only with a layer: nothing is written)
+                host = frames.cpu().numpy()
+                return [host[i] for i in range(host.shape[0])]
             os.makedirs(output_path, exist_ok=True)
             # (the frames are in the INPUT's channel order, as below: the encoders read B, G, R unless --pretrained-estim)
             if png_on_device:
@@ -392,6 +411,29 @@ def gif_shape(width=None, fps=None):
             raise ValueError("the GIF's frame rate (KBE_GIF_FPS, --gif-fps): frames a second, above 0")
         every = max(1, int(round(25.0 / fps)))
     return width, every
+
+
+def layers_of(pipe, size, bgr=True):
+    """The layers of a Pipeline for frames of `size` = (W, H), or a function that gives it and is asked only with a layer, in the order they
+    are applied -- the caption, then the watermark -- (overlay.layers_for): what it was told, else the environment's twins; [] without
+    either.  ValueError whose text begins with the option at fault."""
+    from . import overlay
+    if getattr(pipe, 'no_layers', False):                           # (slideshow.make: the layers are the show's, not a clip's)
+        return []
+    request = overlay.layers_request(*[getattr(pipe, name, None) for name in overlay.OPTIONS])
+    if request is None:
+        return []
+    W, H = size() if callable(size) else size
+    return overlay.layers_for(request, int(W), int(H), bgr)
+
+
+def with_layers(layers, frames):
+    """The frames, a uint8 [n,H,W,3] tensor in HBM, with every layer composited onto every one of them in place (overlay.apply_layers); without a
+    layer: as they are."""
+    if layers:
+        from . import overlay
+        overlay.apply_layers(frames, layers)
+    return frames
 
 
 def out_width(width=None):
