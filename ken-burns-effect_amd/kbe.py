@@ -38,6 +38,16 @@
         [--overlay-margin M]                           (new: the distance of both layers from the edges their anchors name, default
                                                         max(4, frame width // 32) pixels.  Positions are in frame coordinates, after --width; a
                                                         layer that does not fit inside the frame with its margin is refused)
+        [--lut FILE] [--grade brightness=B,contrast=C,saturation=S,gamma=G] [--look mono|sepia] [--lut-strength S]
+                                                       (new: colour grading -- a 3D lookup table applied on the GPU, with tetrahedral
+                                                        interpolation, to every frame where the frames lie, after width, lens and shutter and
+                                                        before a caption or watermark, which are never graded: FILE is a .cube look file (3D,
+                                                        domain 0..1; more than 33 nodes per axis are resampled to 33); --grade bakes any
+                                                        subset of its keys into such a table, on the encoded values, brightness, contrast and
+                                                        saturation 0..4, gamma 0.1..10, each 1 by default; --look is a named one; the finished
+                                                        grade is --grade and --look first, then the file's table; S above 0 and at most 1,
+                                                        default 1, is how much of it shows: env KBE_LUT, KBE_GRADE, KBE_LOOK, KBE_LUT_STRENGTH.
+                                                        Measured alone: tools/grade_time.py, profiles/grade.json)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -51,14 +61,17 @@ import torch
 
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
                 'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=', 'width=', 'aperture=', 'focus=', 'focus-to=', 'shutter=', 'shutter-samples=', 'y4m',
-                'overlay=', 'overlay-at=', 'overlay-opacity=', 'caption=', 'caption-at=', 'caption-size=', 'font=', 'overlay-margin=']
+                'overlay=', 'overlay-at=', 'overlay-opacity=', 'caption=', 'caption-at=', 'caption-size=', 'font=', 'overlay-margin=',
+                'lut=', 'grade=', 'look=', 'lut-strength=']
 LAYER_OPTIONS = ('overlay', 'overlay-at', 'overlay-opacity', 'caption', 'caption-at', 'caption-size', 'font', 'overlay-margin')
+GRADE_OPTIONS = ('lut', 'grade', 'look', 'lut-strength')
 
 
 def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
            'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None, 'width': None, 'aperture': None, 'focus': None, 'focus-to': None, 'shutter': None, 'shutter-samples': None, 'y4m': False,
            'overlay': None, 'overlay-at': None, 'overlay-opacity': None, 'caption': None, 'caption-at': None, 'caption-size': None, 'font': None, 'overlay-margin': None,
+           'lut': None, 'grade': None, 'look': None, 'lut-strength': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -108,6 +121,11 @@ def parse(argv):
     try:                                                                # the two layers: checked as far as they can be without a frame
         from .overlay import layers_request
         cfg['layers'] = layers_request(*[cfg[name] for name in LAYER_OPTIONS])
+    except ValueError as e:
+        raise SystemExit(str(e))
+    try:                                                                # the grade: the file read, the table baked and all of it checked
+        from .grade import grade_request
+        cfg['graded'] = grade_request(*[cfg[name] for name in GRADE_OPTIONS])
     except ValueError as e:
         raise SystemExit(str(e))
     if cfg['gif-fps'] is not None:
@@ -196,7 +214,7 @@ def main(argv=None):
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'],
                     gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'],
                     shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'], y4m=cfg['y4m'] or None,
-                    **{name.replace('-', '_'): cfg[name] for name in LAYER_OPTIONS})
+                    **{name.replace('-', '_'): cfg[name] for name in LAYER_OPTIONS + GRADE_OPTIONS})
     frames = pipe(image, zoom, cfg['out'], pretrained_estim=cfg['pretrained-estim'])
     print('%d frames of %dx%d written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], cfg['out']))
 

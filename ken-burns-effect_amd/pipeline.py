@@ -30,7 +30,8 @@ from .utils import load_models, resize_image
 class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
                  device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None, shutter=None, shutter_samples=None, y4m=None,
-                 overlay=None, overlay_at=None, overlay_opacity=None, caption=None, caption_at=None, caption_size=None, font=None, overlay_margin=None):
+                 overlay=None, overlay_at=None, overlay_opacity=None, caption=None, caption_at=None, caption_size=None, font=None, overlay_margin=None,
+                 lut=None, grade=None, look=None, lut_strength=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
         # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
         # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
@@ -64,6 +65,12 @@ class Pipeline():
         # file as before
         self.overlay, self.overlay_at, self.overlay_opacity, self.overlay_margin = overlay, overlay_at, overlay_opacity, overlay_margin
         self.caption, self.caption_at, self.caption_size, self.font = caption, caption_at, caption_size, font
+        # lut: the path of a .cube file, a 3D lookup table applied on the GPU to every frame where the frames lie, in HBM, after width, lens
+        # and shutter and before the caption and the watermark, which are never graded (grade.py); grade: "brightness=B,contrast=C,
+        # saturation=S,gamma=G", any subset (or a dict of them), baked into such a table; look: 'mono' or 'sepia'; the finished grade is
+        # grade and look first, then the file's table.  lut_strength: above 0 and at most 1 (default 1), how much of the grade shows.  env
+        # KBE_LUT, KBE_GRADE, KBE_LOOK, KBE_LUT_STRENGTH.  None and no env: no grade, every file as before
+        self.lut, self.grade, self.look, self.lut_strength = lut, grade, look, lut_strength
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -159,8 +166,8 @@ class Pipeline():
 
     @torch.no_grad()
     def render(self, tensorImage, zoom_settings):
-        """The clip's frames as a uint8 [steps,H,W,3] tensor in HBM, and nothing written: what _run renders, with the instance's width, lens
-        and shutter, up to process_kenburns(keep_on_device=True).  For callers that go on with the frames on the device (slideshow.py).  _run is kept
+        """The clip's frames as a uint8 [steps,H,W,3] tensor in HBM, and nothing written: what _run renders, with the instance's width, lens,
+        shutter, grade and layers, up to process_kenburns(keep_on_device=True).  For callers that go on with the frames on the device (slideshow.py).  _run is kept
         byte for byte what it was, so its first half is repeated here: an option that _run learns has to be taught to this method as well
         (tests/test_transition_gpu.py holds the two to the same process_kenburns call)."""
         from .utils import miopen_tuned_once
@@ -179,6 +186,7 @@ class Pipeline():
             open_for = shutter_request(getattr(self, 'shutter', None), getattr(self, 'shutter_samples', None))
             # (the layers' colour bytes in the frames' order: B, G, R, unless the caller fed R, G, B and says so in self.overlay_bgr)
             layers = layers_of(self, out_size or (lambda: (tensorImage.size(3), tensorImage.size(2))), bgr=getattr(self, 'overlay_bgr', True))
+            graded = grade_of(self, bgr=getattr(self, 'overlay_bgr', True))
             with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
                 self.estimate(tensorImage)
                 lens = {}
@@ -186,11 +194,11 @@ class Pipeline():
                     from . import dof
                     aperture, near, far = lens_at
                     lens = {'lens': dof.Lens(dof.focus_depth(self.objectCommon['tensorRawDepth'], *near), dof.focus_depth(self.objectCommon['tensorRawDepth'], *far), aperture)}
-                return with_layers(layers, common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
+                return with_layers(layers, with_grade(graded, common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                                 'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                                 'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=True,
                                                **({} if out_size is None else {'out_size': out_size}), **lens,
-                                               **({} if open_for is None else {'shutter': open_for})))
+                                               **({} if open_for is None else {'shutter': open_for}))))
 
     def tuning_tag(self, width, height):
         """What MIOpen is tuned for, once per machine (utils.miopen_tuned_once): this pipeline's networks at this image size."""
@@ -230,6 +238,9 @@ class Pipeline():
         # KBE_OVERLAY, KBE_CAPTION and their kin (Pipeline(overlay=, caption=, ...), kbe.py --overlay --caption): the file is read and the caption
         # drawn before any network runs too, for frames of the size they will have; the frames then stay in HBM, where the layers are composited
         layers = layers_of(self, out_size or (lambda: (tensorImage.size(3), tensorImage.size(2))), bgr=not pretrained_estim)
+        # KBE_LUT, KBE_GRADE, KBE_LOOK, KBE_LUT_STRENGTH (Pipeline(lut=, grade=, look=, lut_strength=), kbe.py --lut --grade --look): the file is
+        # read and the table baked before any network runs too; the frames then stay in HBM, where they are graded before the layers go on
+        graded = grade_of(self, bgr=not pretrained_estim)
         with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
             self.estimate(tensorImage)
             if inpaint_depth:
@@ -242,7 +253,7 @@ class Pipeline():
             jpeg_on_device = output_path is not None and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
             png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
             video_from_hbm = jpeg_on_device and (png_on_device or not self.output_frames)
-            on_device = png_on_device or video_from_hbm or gif_on or y4m_on or bool(layers)
+            on_device = png_on_device or video_from_hbm or gif_on or y4m_on or bool(layers) or graded is not None
             lens = {}
             if lens_at is not None:
                 from . import dof
@@ -254,8 +265,9 @@ class Pipeline():
                                              **({} if out_size is None else {'out_size': out_size}), **lens,
                                              **({} if open_for is None else {'shutter': open_for}))     # (without a width, a lens or a shutter the call is what it was)
         if on_device:
+            with_grade(graded, frames)                                                  # the grade: in place, before the layers, which are never graded
             with_layers(layers, frames)                                                 # the caption, then the watermark: in place, before every output
-            if output_path is None:                                                     # (only with a layer: nothing is written)
+            if output_path is None:                                                     # (only with a grade or a layer: nothing is written)
                 host = frames.cpu().numpy()
                 return [host[i] for i in range(host.shape[0])]
             os.makedirs(output_path, exist_ok=True)
@@ -425,6 +437,21 @@ def layers_of(pipe, size, bgr=True):
         return []
     W, H = size() if callable(size) else size
     return overlay.layers_for(request, int(W), int(H), bgr)
+
+
+def grade_of(pipe, bgr=True):
+    """The grade of a Pipeline for frames in the channel order bgr (grade.grade_for): what it was told, else the environment's twins -- read,
+    checked and baked here, on the host, before any network runs; None without one.  ValueError whose text begins with the option at fault."""
+    from . import grade
+    return grade.grade_for(grade.grade_request(*[getattr(pipe, name, None) for name in grade.OPTIONS]), bgr)
+
+
+def with_grade(graded, frames):
+    """The frames, a uint8 [n,H,W,3] tensor in HBM, graded in place (grade.apply_grade); without a grade they are returned as they are."""
+    if graded is not None:
+        from . import grade
+        grade.apply_grade(frames, graded)
+    return frames
 
 
 def with_layers(layers, frames):

@@ -14,6 +14,10 @@
         [--overlay FILE]                               (a watermark on every frame of the joined show, at a constant opacity: it does not dim
                                                         under a fade) with kbe.py's [--overlay-at A] [--overlay-opacity O] [--caption-at A]
                                                         [--caption-size PX] [--font PATH] [--overlay-margin M]
+        [--lut FILE] [--grade K=V,...] [--look mono|sepia] [--lut-strength S]
+                                                       (kbe.py's colour grading: every clip is graded on the GPU where Pipeline.render leaves it,
+                                                        so transitions blend graded frames; the fade colour, the captions and the watermark are
+                                                        not graded.  One grade for the whole show)
         and of kbe.py's options: [--dolly] [--width N] [--aperture A] [--focus U,V] [--focus-to U,V] [--shutter F] [--shutter-samples S]
         [--gif] [--gif-dither none|ordered] [--gif-width N] [--gif-fps F] [--y4m] [--write-frames] [--jpeg native|pillow|device]
         [--png native|device] [--inpaint-path P] [--refine-path P] [--estim-path P] [--inpaint-depth P] [--pretrained-refine]
@@ -185,6 +189,7 @@ def make(images, out_dir, pipe, transition_kind='dissolve', transition_frames=12
                    width=width, dolly=bool(pipe.dolly), names=names, captions=captions, caption_fade=caption_fade)
     bgr = not pretrained_estim                                      # (the frames are in the INPUT's channel order: B, G, R unless --pretrained-estim)
     titles, watermark = show_layers(show, layers, bgr)
+    P.grade_of(pipe, bgr)                                           # (the clips' grade, which pipe.render applies: refused here, before a network runs)
     gif_on = out_dir is not None and bool(gif)
     if gif_on:
         gif_wide, gif_every = P.gif_shape(getattr(pipe, 'gif_width', None), getattr(pipe, 'gif_fps', None))
@@ -192,10 +197,11 @@ def make(images, out_dir, pipe, transition_kind='dissolve', transition_frames=12
             raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif_wide, show['size'][0]))
     R, G, B = show['colour']
     held, pipe.no_layers = getattr(pipe, 'no_layers', False), True  # (the layers are the show's: a clip is rendered without the Pipeline's own)
+    order, pipe.overlay_bgr = getattr(pipe, 'overlay_bgr', True), bgr  # (... and graded, if the Pipeline has a grade, in the frames' channel order)
     try:
         clips = [pipe.render(image, zoom) for image, zoom in zip(images, show['zooms'])]
     finally:
-        pipe.no_layers = held
+        pipe.no_layers, pipe.overlay_bgr = held, order
     with P.common.on_device_of(pipe.device):
         for clip, title in zip(clips, titles):
             if title is not None:
@@ -269,7 +275,8 @@ def main(argv=None):
     pipe = Pipeline(model_paths=paths, dolly=cfg['dolly'], output_frames=cfg['write-frames'], pretrain=cfg['pretrained-refine'], d2=cfg['2d'],
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif_dither=cfg['gif-dither'],
                     gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'],
-                    shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'], steps=STEPS)
+                    shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'], steps=STEPS,
+                    **{name.replace('-', '_'): cfg[name] for name in kbe.GRADE_OPTIONS})
     frames = make(images, cfg['out'], pipe, pretrained_estim=cfg['pretrained-estim'], gif=cfg['gif'], y4m=cfg['y4m'], names=cfg['in'], layers=cfg['layers'], **settings)
     print('%d frames of %dx%d from %d photos written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], len(images), cfg['out']))
 
