@@ -498,7 +498,7 @@ KBE_API int kbe_bias_act(const float* x, const float* bias, const float* slope, 
 /* nn.Upsample(scale_factor=2, mode='bilinear', align_corners=False) and the nn.PReLU behind it, the head of an `Upsample` block
    (models/pointcloud_inpainting.py:54-80), in one pass: x [B,C,H,W] -> out [B,C,2H,2W]; slope [C] or NULL (no activation).
    Source positions and weights as PyTorch's upsample_bilinear2d computes them (0.5 (dst + 0.5) - 0.5 clamped at 0, the
-   neighbour clamped at the edge). */
+   neighbour clamped at the edge).  x != out.  B C <= 65535 and 2 H <= 65535 (callers ask HipKernels.fused_layers_take, _native.py). */
 KBE_API int kbe_upsample2x_act(const float* x, const float* slope, int B, int C, int H, int W, float* out, kbe_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------

@@ -808,6 +808,16 @@ class HipKernels:
         self._call('kbe_upsample2x_act', _ptr(x), _ptr(None if slope is None else _f32c(slope)), B, C, H, W, _ptr(out), _stream())
         return out
 
+    @staticmethod
+    def fused_layers_take(shape, upsample=False):
+        """Do the fused passes of the plain networks take a [B,C,H,W] tensor -- bias_act as its x, and with ``upsample`` upsample2x_act
+        as its input?  Their grids hold a plane in one block row (B C <= 65535) and upsample2x_act an output row in another
+        (2 H <= 65535); the entries refuse anything above (include/kbe.h).  The ONE place the callers ask (pointcloud_inpainting._fused_layers,
+        _main_fused; partial_inpainting.Upsample.forward): a shape that is not taken runs as the stock modules it would have run without
+        the fused passes."""
+        B, C, H, _ = shape
+        return B * C <= 65535 and (not upsample or 2 * H <= 65535)
+
     pconv_epilogue_adds_bias = True         # (PartialConv2d.forward: run the convolution without its bias)
 
     def pconv_epilogue(self, raw, bias, mask, kernel_size, stride, padding, in_channels=None, in_size=None, act_slope=None, residual=None,

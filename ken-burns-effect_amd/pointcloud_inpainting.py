@@ -44,12 +44,18 @@ def _fused_layers(x):
     if os.environ.get('KBE_FUSED_LAYERS', '1') == '0' or x.device.index != torch.cuda.current_device():
         return None                 # (the C ABI launches on the CURRENT device's stream: a tensor elsewhere takes the stock modules)
     K = common._K()
-    return K if hasattr(K, 'bias_act') else None
+    # (a batch with more planes than the fused passes' grids hold -- B C = 65536 is B = 256 on the 256-channel row -- takes the stock modules)
+    return K if hasattr(K, 'bias_act') and K.fused_layers_take(x.shape) else None
 
 
 def _conv_act(K, conv, act, x, res1=None, res2=None):
     """act(conv(x)) + res1 + res2 with the bias add, the activation and the residuals in ONE pass over the convolution's output
-    (MIOpen's Winograd kernels take no bias: PyTorch adds it -- and everything behind it -- in passes of their own)."""
+    (MIOpen's Winograd kernels take no bias: PyTorch adds it -- and everything behind it -- in passes of their own).  A convolution
+    whose output has more planes than the pass takes (a block that widens its input) runs them as those separate passes."""
+    if not K.fused_layers_take((x.size(0), conv.out_channels) + tuple(x.shape[2:])):
+        y = conv(x) if act is None else act(conv(x))
+        y = y if res1 is None else y + res1
+        return y if res2 is None else y + res2
     y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
     return K.bias_act(y, conv.bias, None if act is None else act.weight, res1, res2, out=y)
 
@@ -61,7 +67,7 @@ def _main_fused(K, seq, x, res1=None, res2=None):
     mods = list(seq)
     x = x.contiguous()
     if isinstance(mods[0], nn.Upsample):
-        x = K.upsample2x_act(x, mods[1].weight)
+        x = K.upsample2x_act(x, mods[1].weight) if K.fused_layers_take(x.shape, upsample=True) else mods[1](mods[0](x))
         mods = mods[2:]
     elif isinstance(mods[0], nn.PReLU):
         x = K.bias_act(x, None, mods[0].weight)
