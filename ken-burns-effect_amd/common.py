@@ -319,7 +319,7 @@ def _prepared_cloud(K, objectCommon):
     return cached[1]
 
 
-def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_out=None, overlap=True, batch=None, out_size=None, lens=None, shutter=None):
+def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_out=None, overlap=True, batch=None, out_size=None, lens=None, shutter=None, enlarge=False):
     """The frame loop proper (common.py:238-257) for a list of (focal, shift3) cameras.
 
     One fused kernel sequence per frame on the resident packed cloud; frames land in one
@@ -337,6 +337,11 @@ def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_o
     the window never sources a fill (deviation 7), so the pixels the patch reads are the ones the cropped route
     would have produced.
 
+    ``enlarge`` = True beside ``out_size``: only then may out_size exceed the crop, w >= crop[0] and h >= crop[1] and at most 16384 each
+    -- the crop's patch enlarged by the exact integer bicubic, one kernel that reads the raw frame and resamples once (enlarge.enlarge;
+    not the bilinear enlargement to W x H enlarged again).  It stands where the reduction stands, on every route below; an out_size
+    within the crop is reduced as without it.
+
     ``lens`` = dof.Lens(focus_from, focus_to, aperture, max_radius): depth of field.  The frames take a route of their own
     (_render_lens): each is rendered on its own with its float render, blurred in HBM by the depth of its pixels (dof.apply), and only
     then cropped and resized, reduced to ``out_size``, or left as it is; host_out, overlap and batch do not apply.  The sharded path does
@@ -348,11 +353,13 @@ def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_o
     samples (shutter.mean), and only the len(cameras) / samples means are returned or fetched; host_out, overlap and batch do not apply.
     The sharded path does not take the argument."""
     if shutter is not None:
-        return _render_shutter(cameras, objectCommon, crop, out_size, keep_on_device, lens, shutter)
+        return _render_shutter(cameras, objectCommon, crop, out_size, keep_on_device, lens, shutter, enlarge)
     if lens is not None:
-        return _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens)
+        return _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens, enlarge=enlarge)
     if out_size is not None:
-        return _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device)
+        return _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device, enlarge)
+    if enlarge:
+        raise ValueError('render_frames(enlarge=True) enlarges the crop to out_size: it needs out_size=(w, h)')
     K = _K()
     W, H = objectCommon['intWidth'], objectCommon['intHeight']
     state = _prepared_cloud(K, objectCommon)
@@ -379,13 +386,22 @@ def render_frames(cameras, objectCommon, crop=None, keep_on_device=False, host_o
     return out if keep_on_device else out.cpu().numpy()
 
 
-def _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device):
-    """render_frames(out_size=...): the raw frames in HBM, then their crop reduced there (crop_area.reduce)."""
+def _resized(frames_in_hbm, crop, out_size, enlarge):
+    """The crop of raw frames in HBM at out_size: enlarged where that was asked for and no side shrinks (enlarge.enlarge), else reduced
+    (crop_area.reduce); each refuses what it does not do."""
+    if enlarge and int(out_size[0]) >= int(crop[0]) and int(out_size[1]) >= int(crop[1]):
+        from . import enlarge as enlarge_of
+        return enlarge_of.enlarge(frames_in_hbm, crop, out_size)
     from . import crop_area
+    return crop_area.reduce(frames_in_hbm, crop, out_size)
+
+
+def _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device, enlarge=False):
+    """render_frames(out_size=...): the raw frames in HBM, then their crop reduced or enlarged there (_resized)."""
     if crop is None:
         raise ValueError('render_frames(out_size=...) reduces the crop: it needs crop=(w, h)')
     raw = render_frames(cameras, objectCommon, None, keep_on_device=True)
-    out = crop_area.reduce(raw, crop, out_size)
+    out = _resized(raw, crop, out_size, enlarge)
     if keep_on_device:
         return out
     # (into pinned memory, as the frames of the photo's size land: a copy into pageable memory runs at a seventh of the link's rate)
@@ -395,7 +411,7 @@ def _render_reduced(cameras, objectCommon, crop, out_size, keep_on_device):
     return host.numpy()
 
 
-def _render_shutter(cameras, objectCommon, crop, out_size, keep_on_device, lens, shutter):
+def _render_shutter(cameras, objectCommon, crop, out_size, keep_on_device, lens, shutter, enlarge=False):
     """render_frames(shutter=...): output frames in chunks of max(1, 96 // samples) -- at most 96 samples lie in HBM at a time, one launch of
     the entry --, each chunk's samples rendered by the route they would take without a shutter (keep_on_device), then averaged where they lie
     (shutter.mean).  The mean is taken on FINISHED frames, after the crop and resize or the reduction: with an out_size that is a fraction
@@ -418,9 +434,9 @@ def _render_shutter(cameras, objectCommon, crop, out_size, keep_on_device, lens,
         count = min(chunk, n - first)
         cams = cameras[first * S:(first + count) * S]
         if lens is not None:
-            samples = _render_lens(cams, objectCommon, crop, out_size, True, lens, focus=[focus[first + k // S] for k in range(count * S)])
+            samples = _render_lens(cams, objectCommon, crop, out_size, True, lens, focus=[focus[first + k // S] for k in range(count * S)], enlarge=enlarge)
         else:
-            samples = render_frames(cams, objectCommon, crop, keep_on_device=True, out_size=out_size)
+            samples = render_frames(cams, objectCommon, crop, keep_on_device=True, out_size=out_size, enlarge=enlarge)
         mean = shutter_of.mean(samples, S)
         if count == n:
             out = mean
@@ -437,13 +453,13 @@ def _render_shutter(cameras, objectCommon, crop, out_size, keep_on_device, lens,
     return host.numpy()
 
 
-def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens, focus=None):
+def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens, focus=None, enlarge=False):
     """render_frames(lens=...): groups of at most twelve frames, each frame rendered by K.render_frame with its float render (plane 3: the
     depth of every pixel, hole-filled) and no fill rectangle -- the blur reads beyond the crop's window --, the group blurred where it lies
-    (dof.apply: one launch), then crop_area.reduce (out_size), K.crop_resize_u8 per frame (crop alone) or nothing more.  The focus
+    (dof.apply: one launch), then _resized (out_size: reduced, or with ``enlarge`` enlarged), K.crop_resize_u8 per frame (crop alone) or nothing more.  The focus
     depth of frame i is dof.focus_path(focus_from, focus_to, n)[i], or ``focus``[i] where the caller gives one depth per camera
     (_render_shutter: the samples of one exposure share a depth)."""
-    from . import crop_area, dof
+    from . import dof
     if out_size is not None and crop is None:
         raise ValueError('render_frames(out_size=...) reduces the crop: it needs crop=(w, h)')
     lens = dof.checked_lens(lens)
@@ -470,7 +486,7 @@ def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens, fo
             K.render_frame(state, shift3, focal, objectCommon['dblBaseline'], render_f32=render[k], out=raw[k], fill_rect=None)
         blurred = dof.apply(raw[:count], render[:count, 3], focus[first:first + count], lens.aperture, lens.max_radius)
         if out_size is not None:
-            out[first:first + count].copy_(crop_area.reduce(blurred, crop, out_size))
+            out[first:first + count].copy_(_resized(blurred, crop, out_size, enlarge))
         elif crop is not None:
             for k in range(count):
                 out[first + k].copy_(K.crop_resize_u8(blurred[k], crop[0], crop[1]))
@@ -484,7 +500,7 @@ def _render_lens(cameras, objectCommon, crop, out_size, keep_on_device, lens, fo
     return host.numpy()
 
 
-def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False, out_size=None, lens=None, shutter=None):
+def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device=False, out_size=None, lens=None, shutter=None, enlarge=False):
     """Renders the camera path ``dblSteps`` between two crop windows (common.py:172-263).
 
     objectSettings: dblSteps, objectFrom/objectTo {dblCenterU, dblCenterV, intCropWidth,
@@ -493,7 +509,8 @@ def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device
     come back as one uint8 [n,H,W,3] device tensor (for the device-side Motion-JPEG encoder).  ``out_size`` = (w, h): frames of that size,
     the crop reduced on the GPU and never enlarged (render_frames(out_size=...)); it needs the crop (``boolCrop``).  ``lens``: depth of
     field (render_frames(lens=...)).  ``shutter``: motion blur -- every step of ``dblSteps`` becomes ``samples`` steps around it
-    (shutter.sample_steps), rendered and averaged on the GPU (render_frames(shutter=...)); as many frames as steps come back."""
+    (shutter.sample_steps), rendered and averaged on the GPU (render_frames(shutter=...)); as many frames as steps come back.
+    ``enlarge`` = True beside ``out_size``: the size may exceed the crop, which is then enlarged on the GPU (render_frames(enlarge=True))."""
     with on_device_of(objectCommon['tensorRawPoints']):
         if 'boolInpaint' not in objectSettings or objectSettings['boolInpaint'] == True:   # noqa: E712
             build_pointcloud(objectSettings, objectCommon, moduleInpaint)
@@ -503,7 +520,7 @@ def process_kenburns(objectSettings, objectCommon, moduleInpaint, keep_on_device
             shutter = shutter_of.checked(shutter)
             objectSettings = dict(objectSettings, dblSteps=shutter_of.sample_steps(objectSettings['dblSteps'], shutter.fraction, shutter.samples))
         frames = render_frames(frame_cameras(objectSettings, objectCommon), objectCommon, crop, keep_on_device=keep_on_device, out_size=out_size,
-                               **({} if lens is None else {'lens': lens}), **({} if shutter is None else {'shutter': shutter}))
+                               **({} if lens is None else {'lens': lens}), **({} if shutter is None else {'shutter': shutter}), **({'enlarge': True} if enlarge else {}))
     if keep_on_device:
         return frames
     return [frames[i] for i in range(frames.shape[0])]

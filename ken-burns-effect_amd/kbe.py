@@ -13,6 +13,11 @@
         [--width N]                                    (new: every output -- the video, the PNG frames, the GIF -- N pixels wide, the height by the image's
                                                         aspect ratio: the crop reduced on the GPU by an exact area average, never enlarged, so N is
                                                         at most the crop's width; --gif-width is then at most N: env KBE_WIDTH)
+        [--enlarge]                                    (new: with --width, N may exceed the crop's width, up to four times it and 16384 pixels a
+                                                        side: the crop is then enlarged on the GPU by an exact integer Catmull-Rom bicubic, in
+                                                        one resampling from the crop's patch, for a 1080p or 4K clip; an N within the crop is
+                                                        reduced as without it: env KBE_ENLARGE=1.  Measured alone: tools/enlarge_time.py,
+                                                        profiles/enlarge.json)
         [--aperture A] [--focus U,V] [--focus-to U,V]  (new: depth of field, a lens blur on the GPU from each frame's depth -- A is the blur radius in
                                                         pixels of a point at infinity, above 0; what lies at the depth of pixel U,V of the photo
                                                         stays sharp (default: the centre of the end window), and with --focus-to the focus is pulled
@@ -62,7 +67,7 @@ import torch
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
                 'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=', 'width=', 'aperture=', 'focus=', 'focus-to=', 'shutter=', 'shutter-samples=', 'y4m',
                 'overlay=', 'overlay-at=', 'overlay-opacity=', 'caption=', 'caption-at=', 'caption-size=', 'font=', 'overlay-margin=',
-                'lut=', 'grade=', 'look=', 'lut-strength=']
+                'lut=', 'grade=', 'look=', 'lut-strength=', 'enlarge']
 LAYER_OPTIONS = ('overlay', 'overlay-at', 'overlay-opacity', 'caption', 'caption-at', 'caption-size', 'font', 'overlay-margin')
 GRADE_OPTIONS = ('lut', 'grade', 'look', 'lut-strength')
 
@@ -71,7 +76,7 @@ def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
            'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None, 'width': None, 'aperture': None, 'focus': None, 'focus-to': None, 'shutter': None, 'shutter-samples': None, 'y4m': False,
            'overlay': None, 'overlay-at': None, 'overlay-opacity': None, 'caption': None, 'caption-at': None, 'caption-size': None, 'font': None, 'overlay-margin': None,
-           'lut': None, 'grade': None, 'look': None, 'lut-strength': None,
+           'lut': None, 'grade': None, 'look': None, 'lut-strength': None, 'enlarge': False,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -80,7 +85,7 @@ def parse(argv):
         if name in window:
             if argument != '':
                 window[name] = int(argument)
-        elif name in ('dolly', 'write-frames', 'pretrained-refine', 'pretrained-estim', '2d', 'allow-random-weights', 'gif', 'y4m'):
+        elif name in ('dolly', 'write-frames', 'pretrained-refine', 'pretrained-estim', '2d', 'allow-random-weights', 'gif', 'y4m', 'enlarge'):
             cfg[name] = True
         elif argument != '' or name == 'caption':                        # (an empty caption is refused below, not passed over)
             cfg[name] = argument
@@ -101,6 +106,8 @@ def parse(argv):
         cfg['width'] = int(cfg['width'])
         if cfg['gif-width'] is not None and cfg['gif-width'] > cfg['width']:
             raise SystemExit('--gif-width %d: the frames are %d pixels wide (--width), and the GIF is only ever reduced' % (cfg['gif-width'], cfg['width']))
+    if cfg['enlarge'] and cfg['width'] is None:
+        raise SystemExit('--enlarge: only with --width')
     if cfg['aperture'] is not None or cfg['focus'] is not None or cfg['focus-to'] is not None:
         from .pipeline import lens_request
         for name in ('focus', 'focus-to'):
@@ -189,12 +196,13 @@ def main(argv=None):
         import os
         os.environ['KBE_PNG'] = cfg['png']          # (... and pipeline.png_encoder)
     image = load_image(cfg['in'], cfg['pretrained-estim'])
-    if cfg['gif-width'] is not None and cfg['gif-width'] > image.shape[3]:
+    if cfg['gif-width'] is not None and cfg['gif-width'] > image.shape[3] and not cfg['enlarge']:      # (with --enlarge: at most --width, checked by parse)
         raise SystemExit('--gif-width %d: the image is %d pixels wide, and the GIF is only ever reduced' % (cfg['gif-width'], image.shape[3]))
     zoom = windows_for(image.shape[3], image.shape[2], window, cfg['dolly'])
+    enlarging = {'enlarge': True} if cfg['enlarge'] else {}
     if cfg['width'] is not None:
         try:                                                                # (before any network is built)
-            width_size(cfg['width'], image.shape[3], image.shape[2], zoom)
+            width_size(cfg['width'], image.shape[3], image.shape[2], zoom, **enlarging)
         except ValueError as e:
             raise SystemExit('--width %d: %s' % (cfg['width'], e))
     if cfg['aperture'] is not None:
@@ -205,7 +213,7 @@ def main(argv=None):
     if cfg['layers'] is not None:
         from .overlay import layers_for
         try:                                                                # (... and the file read, the caption drawn and both fitted to the frames)
-            layers_for(cfg['layers'], *(width_size(cfg['width'], image.shape[3], image.shape[2], zoom) if cfg['width'] is not None else (image.shape[3], image.shape[2])),
+            layers_for(cfg['layers'], *(width_size(cfg['width'], image.shape[3], image.shape[2], zoom, **enlarging) if cfg['width'] is not None else (image.shape[3], image.shape[2])),
                        bgr=not cfg['pretrained-estim'])
         except ValueError as e:
             raise SystemExit(str(e))
@@ -214,7 +222,7 @@ def main(argv=None):
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'],
                     gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'],
                     shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'], y4m=cfg['y4m'] or None,
-                    **{name.replace('-', '_'): cfg[name] for name in LAYER_OPTIONS + GRADE_OPTIONS})
+                    **{name.replace('-', '_'): cfg[name] for name in LAYER_OPTIONS + GRADE_OPTIONS}, **enlarging)
     frames = pipe(image, zoom, cfg['out'], pretrained_estim=cfg['pretrained-estim'])
     print('%d frames of %dx%d written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], cfg['out']))
 

@@ -31,7 +31,7 @@ class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
                  device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None, shutter=None, shutter_samples=None, y4m=None,
                  overlay=None, overlay_at=None, overlay_opacity=None, caption=None, caption_at=None, caption_size=None, font=None, overlay_margin=None,
-                 lut=None, grade=None, look=None, lut_strength=None):
+                 lut=None, grade=None, look=None, lut_strength=None, enlarge=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
         # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
         # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
@@ -43,6 +43,10 @@ class Pipeline():
         # enlarged, so at most the crop's size (common.crop_size of the zoom settings); env KBE_WIDTH.  gif_width is then taken against
         # the reduced frames.  None and no env: the image's size, every file as before
         self.width = width
+        # enlarge: a width above the crop's is taken, up to four times it: the crop is then enlarged on the GPU by an exact integer bicubic
+        # (enlarge.py), straight from the crop's patch and not from the frames of the image's size; a width within the crop is reduced as
+        # without the switch; env KBE_ENLARGE=1.  None and no env: a width above the crop's is refused, every file as before
+        self.enlarge = enlarge
         # aperture: depth of field -- the blur radius, in pixels of the raw frame, of a point at infinity, above 0 and finite; what lies at the
         # focus depth stays sharp (dof.py, common.render_frames(lens=)); env KBE_APERTURE.  focus = (u, v): the pixel of the photo to focus on
         # (default: the centre of the end window); focus_to = (u, v): the focus is pulled there over the clip, linearly in 1 / depth (default:
@@ -174,12 +178,16 @@ class Pipeline():
         with common.on_device_of(getattr(self, 'device', torch.device('cpu'))):
             auto = getattr(self, 'miopen_find', False) == 'auto'
             wide = out_width(getattr(self, 'width', None))
+            enlarging = {'enlarge': True} if enlarge_switch(getattr(self, 'enlarge', None)) else {}
             out_size = None
             if wide is not None:
                 try:
-                    out_size = width_size(wide, tensorImage.size(3), tensorImage.size(2), zoom_settings)
+                    out_size = width_size(wide, tensorImage.size(3), tensorImage.size(2), zoom_settings, **enlarging)
                 except ValueError as e:
                     raise ValueError('width %d: %s' % (wide, e)) from None
+            elif enlarging:
+                raise ValueError('enlarge (KBE_ENLARGE, --enlarge): only with a width')
+            grow = {'enlarge': True} if out_size is not None and grows(out_size, zoom_settings) else {}
             lens_at = lens_request(getattr(self, 'aperture', None), getattr(self, 'focus', None), getattr(self, 'focus_to', None))
             if lens_at is not None:
                 lens_at = lens_points(lens_at, tensorImage.size(3), tensorImage.size(2), zoom_settings)
@@ -197,7 +205,7 @@ class Pipeline():
                 return with_layers(layers, with_grade(graded, common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                                 'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                                 'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=True,
-                                               **({} if out_size is None else {'out_size': out_size}), **lens,
+                                               **({} if out_size is None else {'out_size': out_size}), **grow, **lens,
                                                **({} if open_for is None else {'shutter': open_for}))))
 
     def tuning_tag(self, width, height):
@@ -214,20 +222,25 @@ class Pipeline():
         gif_on = output_path is not None and gif_switch(getattr(self, 'gif', None))
         if gif_on:
             gif_wide, gif_every = gif_shape(getattr(self, 'gif_width', None), getattr(self, 'gif_fps', None))
-            if gif_wide is not None and gif_wide > tensorImage.size(3):
+            if gif_wide is not None and gif_wide > tensorImage.size(3) and not enlarge_switch(getattr(self, 'enlarge', None)):      # (enlarged frames may be wider: see below)
                 raise ValueError('a GIF %d pixels wide from an image %d wide: the GIF is only ever reduced' % (gif_wide, tensorImage.size(3)))
         # KBE_Y4M=1 (Pipeline(y4m=True), kbe.py --y4m): the frames stay in HBM as with the GIF, and 3d_kbe.y4m is converted from them (yuv.py)
         y4m_on = output_path is not None and y4m_switch(getattr(self, 'y4m', None))
         # KBE_WIDTH (Pipeline(width=), kbe.py --width): looked at before any network runs as well
         wide = out_width(getattr(self, 'width', None))
+        # KBE_ENLARGE=1 (Pipeline(enlarge=True), kbe.py --enlarge): a width above the crop's is then taken, and the crop enlarged (enlarge.py)
+        enlarging = {'enlarge': True} if enlarge_switch(getattr(self, 'enlarge', None)) else {}
         out_size = None
         if wide is not None:
             try:
-                out_size = width_size(wide, tensorImage.size(3), tensorImage.size(2), zoom_settings)
+                out_size = width_size(wide, tensorImage.size(3), tensorImage.size(2), zoom_settings, **enlarging)
             except ValueError as e:
                 raise ValueError('width %d: %s' % (wide, e)) from None
             if gif_on and gif_wide is not None and gif_wide > out_size[0]:
                 raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif_wide, out_size[0]))
+        elif enlarging:
+            raise ValueError('enlarge (KBE_ENLARGE, --enlarge): only with a width')
+        grow = {'enlarge': True} if out_size is not None and grows(out_size, zoom_settings) else {}
         # KBE_APERTURE, KBE_FOCUS, KBE_FOCUS_TO (Pipeline(aperture=, focus=, focus_to=), kbe.py --aperture --focus --focus-to): looked at
         # before any network runs as well; the focus DEPTHS are read from the estimated depth below
         lens_at = lens_request(getattr(self, 'aperture', None), getattr(self, 'focus', None), getattr(self, 'focus_to', None))
@@ -262,7 +275,7 @@ class Pipeline():
             frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                               'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                               'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device,
-                                             **({} if out_size is None else {'out_size': out_size}), **lens,
+                                             **({} if out_size is None else {'out_size': out_size}), **grow, **lens,
                                              **({} if open_for is None else {'shutter': open_for}))     # (without a width, a lens or a shutter the call is what it was)
         if on_device:
             with_grade(graded, frames)                                                  # the grade: in place, before the layers, which are never graded
@@ -477,11 +490,38 @@ def out_width(width=None):
     return width
 
 
-def width_size(width, W, H, zoom_settings):
+def enlarge_switch(enlarge=None):
+    """Whether a width above the crop's is taken, the crop then enlarged (enlarge.py): what Pipeline was told, else env KBE_ENLARGE=1
+    (kbe.py --enlarge).  Off by default."""
+    return bool(enlarge) if enlarge is not None else os.environ.get('KBE_ENLARGE', '0') == '1'
+
+
+ENLARGE_FOLD = 4          # the widest output of the switch, in crop widths
+
+
+def grows(size, zoom_settings):
+    """Whether outputs of this (w, h) are larger than the crop of the zoom settings on a side: the frames are then enlarged, not reduced."""
+    crop_w, crop_h = (int(v) for v in common.crop_size(zoom_settings))
+    return size[0] > crop_w or size[1] > crop_h
+
+
+def width_size(width, W, H, zoom_settings, enlarge=False):
     """(w, h) of outputs `width` wide from a W x H image: the height follows the image's aspect ratio (crop_area.size_for).  The frames are
-    the crop of the zoom settings (common.crop_size) reduced, never enlarged: a width, or its height, above the crop's is refused."""
+    the crop of the zoom settings (common.crop_size) reduced, never enlarged: a width, or its height, above the crop's is refused.
+    With ``enlarge`` a width above the crop's is taken, up to ENLARGE_FOLD times it and 16384 pixels a side: the crop is then enlarged
+    (grows); one that lets one side grow and the other shrink -- by rounding, near the crop's own size -- is refused."""
     from . import crop_area
     crop_w, crop_h = (int(v) for v in common.crop_size(zoom_settings))
+    if enlarge:
+        from . import enlarge as enlarge_of
+        if width > ENLARGE_FOLD * crop_w:
+            raise ValueError('the crop is %d pixels wide: outputs are enlarged at most %d-fold, to %d' % (crop_w, ENLARGE_FOLD, ENLARGE_FOLD * crop_w))
+        w, h = enlarge_of.size_for(W, H, width)
+        if (w > crop_w and h < crop_h) or (w < crop_w and h > crop_h):
+            raise ValueError('the outputs are then %dx%d and the crop is %dx%d: one side would grow and the other shrink' % (w, h, crop_w, crop_h))
+        if (w > crop_w or h > crop_h) and max(w, h) > enlarge_of.MAX_SIDE:
+            raise ValueError('the outputs are then %dx%d: an enlarged side is at most %d pixels' % (w, h, enlarge_of.MAX_SIDE))
+        return w, h
     if width > crop_w:
         raise ValueError('the crop is %d pixels wide: outputs are only ever reduced' % crop_w)
     w, h = crop_area.size_for(W, H, width=width)

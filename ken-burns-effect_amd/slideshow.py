@@ -18,7 +18,7 @@
                                                        (kbe.py's colour grading: every clip is graded on the GPU where Pipeline.render leaves it,
                                                         so transitions blend graded frames; the fade colour, the captions and the watermark are
                                                         not graded.  One grade for the whole show)
-        and of kbe.py's options: [--dolly] [--width N] [--aperture A] [--focus U,V] [--focus-to U,V] [--shutter F] [--shutter-samples S]
+        and of kbe.py's options: [--dolly] [--width N] [--enlarge] [--aperture A] [--focus U,V] [--focus-to U,V] [--shutter F] [--shutter-samples S]
         [--gif] [--gif-dither none|ordered] [--gif-width N] [--gif-fps F] [--y4m] [--write-frames] [--jpeg native|pillow|device]
         [--png native|device] [--inpaint-path P] [--refine-path P] [--estim-path P] [--inpaint-depth P] [--pretrained-refine]
         [--pretrained-estim] [--2d] [--semantics-path P] [--allow-random-weights]
@@ -64,10 +64,11 @@ def colour_bytes(text):
     return tuple(values)
 
 
-def frame_size(W, H, zoom, width=None):
-    """(w, h) of the frames a W x H photo gives under these windows: the photo's size, or --width's (pipeline.width_size)."""
+def frame_size(W, H, zoom, width=None, enlarge=False):
+    """(w, h) of the frames a W x H photo gives under these windows: the photo's size, or --width's (pipeline.width_size; with ``enlarge``
+    it may exceed the crop's)."""
     from .pipeline import width_size
-    return (int(W), int(H)) if width is None else width_size(width, W, H, zoom)
+    return (int(W), int(H)) if width is None else width_size(width, W, H, zoom, **({'enlarge': True} if enlarge else {}))
 
 
 def caption_windows(steps, photos, T, fade_in=0, fade_out=0):
@@ -94,11 +95,13 @@ def show_layers(show, request, bgr=True):
 
 
 def checked(sizes, steps, transition_kind='dissolve', transition_frames=12, softness=None, fade_colour=(0, 0, 0), fade_in=0, fade_out=0, width=None, dolly=False, names=None,
-            captions=None, caption_fade=12):
+            captions=None, caption_fade=12, enlarge=False):
     """What a slideshow of photos of these (W, H) sizes will be, from the sizes, the default windows and the width alone -- before any network runs:
     {'size': (w, h) of every frame, 'zooms', 'kind', 'T', 'softness', 'colour': (R, G, B), 'fade_in', 'fade_out', 'plan': transition.join_plan's,
     'steps', 'captions': one text per photo or None, 'caption_fade', 'windows': caption_windows'}, or ValueError whose text begins with the option at fault."""
     names = list(names) if names is not None else ['photo %d' % i for i in range(len(sizes))]
+    if enlarge and width is None:
+        raise ValueError('--enlarge: only with --width')
     if len(sizes) < 1:
         raise ValueError('--in: a slideshow takes one photo or more')
     if transition_kind not in transition.KINDS:
@@ -130,7 +133,7 @@ def checked(sizes, steps, transition_kind='dissolve', transition_frames=12, soft
     for i, (W, H) in enumerate(sizes):
         zooms.append(kbe.windows_for(W, H, NO_WINDOW, dolly))
         try:
-            mine = frame_size(W, H, zooms[-1], width)
+            mine = frame_size(W, H, zooms[-1], width, enlarge)
         except ValueError as e:
             raise ValueError('--width %d: %s: %s' % (width, names[i], e)) from None
         if size is None:
@@ -186,7 +189,7 @@ def make(images, out_dir, pipe, transition_kind='dissolve', transition_frames=12
     from . import pipeline as P
     width = P.out_width(getattr(pipe, 'width', None))
     show = checked([(int(t.shape[3]), int(t.shape[2])) for t in images], pipe.steps, transition_kind, transition_frames, softness, fade_colour, fade_in, fade_out,
-                   width=width, dolly=bool(pipe.dolly), names=names, captions=captions, caption_fade=caption_fade)
+                   width=width, dolly=bool(pipe.dolly), names=names, captions=captions, caption_fade=caption_fade, enlarge=P.enlarge_switch(getattr(pipe, 'enlarge', None)))
     bgr = not pretrained_estim                                      # (the frames are in the INPUT's channel order: B, G, R unless --pretrained-estim)
     titles, watermark = show_layers(show, layers, bgr)
     P.grade_of(pipe, bgr)                                           # (the clips' grade, which pipe.render applies: refused here, before a network runs)
@@ -258,7 +261,7 @@ def main(argv=None):
     settings = dict(transition_kind=cfg['transition'], transition_frames=cfg['transition-frames'], softness=cfg['softness'], fade_colour=cfg['fade-colour'],
                     fade_in=cfg['fade-in'], fade_out=cfg['fade-out'], captions=cfg['caption'], caption_fade=cfg['caption-fade'])
     try:                                                                # (before any network is built)
-        show = checked([(int(t.shape[3]), int(t.shape[2])) for t in images], STEPS, width=cfg['width'], dolly=cfg['dolly'], names=cfg['in'], **settings)
+        show = checked([(int(t.shape[3]), int(t.shape[2])) for t in images], STEPS, width=cfg['width'], dolly=cfg['dolly'], names=cfg['in'], enlarge=cfg['enlarge'], **settings)
         show_layers(show, cfg['layers'], not cfg['pretrained-estim'])
     except ValueError as e:
         raise SystemExit(str(e))
@@ -276,7 +279,7 @@ def main(argv=None):
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif_dither=cfg['gif-dither'],
                     gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'],
                     shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'], steps=STEPS,
-                    **{name.replace('-', '_'): cfg[name] for name in kbe.GRADE_OPTIONS})
+                    **{name.replace('-', '_'): cfg[name] for name in kbe.GRADE_OPTIONS}, **({'enlarge': True} if cfg['enlarge'] else {}))
     frames = make(images, cfg['out'], pipe, pretrained_estim=cfg['pretrained-estim'], gif=cfg['gif'], y4m=cfg['y4m'], names=cfg['in'], layers=cfg['layers'], **settings)
     print('%d frames of %dx%d from %d photos written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], len(images), cfg['out']))
 
