@@ -53,6 +53,13 @@
                                                         grade is --grade and --look first, then the file's table; S above 0 and at most 1,
                                                         default 1, is how much of it shows: env KBE_LUT, KBE_GRADE, KBE_LOOK, KBE_LUT_STRENGTH.
                                                         Measured alone: tools/grade_time.py, profiles/grade.json)
+        [--sharpen AMOUNT[,SIGMA[,THRESHOLD]]]         (new: output sharpening -- an exact integer unsharp mask applied on the GPU to every
+                                                        frame where the frames lie, after width, enlargement, lens, shutter and grade, the
+                                                        last thing done to the picture, and before a caption or watermark, which are never
+                                                        sharpened: the frame minus its Gaussian blur of SIGMA pixels, 0.3..8, default 1, is
+                                                        added back AMOUNT times, above 0 and at most 4, wherever it is at least THRESHOLD
+                                                        counts, 0..255, default 0: env KBE_SHARPEN.  Measured alone: tools/sharpen_time.py,
+                                                        profiles/sharpen.json)
 
 Images are read with PIL (OpenCV is not a dependency); like ``cv2.imread`` the pixels are handed to the
 networks in BGR order unless ``--pretrained-estim`` is given (kbe.py:96-98).
@@ -67,7 +74,7 @@ import torch
 LONG_OPTIONS = ['in=', 'out=', 'dolly', 'write-frames', 'inpaint-path=', 'refine-path=', 'estim-path=', 'startU=', 'startV=', 'endU=',
                 'endV=', 'startW=', 'startH=', 'endW=', 'endH=', 'pretrained-refine', 'pretrained-estim', 'inpaint-depth=', '2d', 'semantics-path=', 'allow-random-weights', 'jpeg=', 'png=', 'gif', 'gif-dither=', 'gif-width=', 'gif-fps=', 'width=', 'aperture=', 'focus=', 'focus-to=', 'shutter=', 'shutter-samples=', 'y4m',
                 'overlay=', 'overlay-at=', 'overlay-opacity=', 'caption=', 'caption-at=', 'caption-size=', 'font=', 'overlay-margin=',
-                'lut=', 'grade=', 'look=', 'lut-strength=', 'enlarge']
+                'lut=', 'grade=', 'look=', 'lut-strength=', 'enlarge', 'sharpen=']
 LAYER_OPTIONS = ('overlay', 'overlay-at', 'overlay-opacity', 'caption', 'caption-at', 'caption-size', 'font', 'overlay-margin')
 GRADE_OPTIONS = ('lut', 'grade', 'look', 'lut-strength')
 
@@ -76,7 +83,7 @@ def parse(argv):
     cfg = {'in': 'images/doublestrike.jpg', 'out': 'images/kbe', 'dolly': False, 'write-frames': False, 'pretrained-refine': False,
            'pretrained-estim': False, '2d': False, 'inpaint-depth': None, 'semantics-path': None, 'allow-random-weights': False, 'jpeg': None, 'png': None, 'gif': False, 'gif-dither': None, 'gif-width': None, 'gif-fps': None, 'width': None, 'aperture': None, 'focus': None, 'focus-to': None, 'shutter': None, 'shutter-samples': None, 'y4m': False,
            'overlay': None, 'overlay-at': None, 'overlay-opacity': None, 'caption': None, 'caption-at': None, 'caption-size': None, 'font': None, 'overlay-margin': None,
-           'lut': None, 'grade': None, 'look': None, 'lut-strength': None, 'enlarge': False,
+           'lut': None, 'grade': None, 'look': None, 'lut-strength': None, 'enlarge': False, 'sharpen': None,
            'inpaint-path': './models/trained/inpainting-color.tar', 'refine-path': './models/trained/disparity-refinement.tar',
            'estim-path': './models/trained/disparity-estimation-no-mask.tar'}
     window = dict.fromkeys(('startU', 'startV', 'startW', 'startH', 'endU', 'endV', 'endW', 'endH'))
@@ -133,6 +140,11 @@ def parse(argv):
     try:                                                                # the grade: the file read, the table baked and all of it checked
         from .grade import grade_request
         cfg['graded'] = grade_request(*[cfg[name] for name in GRADE_OPTIONS])
+    except ValueError as e:
+        raise SystemExit(str(e))
+    try:                                                                # the sharpening: its three fields checked, the taps made
+        from .sharpen import request as sharpen_request
+        cfg['sharpened'] = sharpen_request(cfg['sharpen'])
     except ValueError as e:
         raise SystemExit(str(e))
     if cfg['gif-fps'] is not None:
@@ -222,7 +234,8 @@ def main(argv=None):
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif=cfg['gif'] or None, gif_dither=cfg['gif-dither'],
                     gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'],
                     shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'], y4m=cfg['y4m'] or None,
-                    **{name.replace('-', '_'): cfg[name] for name in LAYER_OPTIONS + GRADE_OPTIONS}, **enlarging)
+                    **{name.replace('-', '_'): cfg[name] for name in LAYER_OPTIONS + GRADE_OPTIONS}, **enlarging,
+                    **({} if cfg['sharpen'] is None else {'sharpen': cfg['sharpen']}))
     frames = pipe(image, zoom, cfg['out'], pretrained_estim=cfg['pretrained-estim'])
     print('%d frames of %dx%d written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], cfg['out']))
 

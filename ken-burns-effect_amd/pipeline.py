@@ -31,7 +31,7 @@ class Pipeline():
     def __init__(self, model_paths=None, partial_inpainting=False, dolly=False, output_frames=False, pretrain=False, d2=False,
                  device='cuda:0', steps=75, inpaint_dtype=None, semantics_path=None, miopen_find=None, allow_random_weights=None, gif=None, gif_dither=None, gif_width=None, gif_fps=None, width=None, aperture=None, focus=None, focus_to=None, shutter=None, shutter_samples=None, y4m=None,
                  overlay=None, overlay_at=None, overlay_opacity=None, caption=None, caption_at=None, caption_size=None, font=None, overlay_margin=None,
-                 lut=None, grade=None, look=None, lut_strength=None, enlarge=None):
+                 lut=None, grade=None, look=None, lut_strength=None, enlarge=None, sharpen=None):
         # gif: also write 3d_kbe.gif, encoded on the GPU (gif.py), beside the video; None: env KBE_GIF=1.  gif_dither: 'ordered' (the
         # default; env KBE_GIF_DITHER) or 'none'.  Opt-in: without it every file is written as before.  gif_width: the GIF's width in pixels, at
         # most the frames' -- reduced on the GPU by an exact area average (area.py), the height follows the aspect ratio; env KBE_GIF_WIDTH.
@@ -75,6 +75,11 @@ class Pipeline():
         # grade and look first, then the file's table.  lut_strength: above 0 and at most 1 (default 1), how much of the grade shows.  env
         # KBE_LUT, KBE_GRADE, KBE_LOOK, KBE_LUT_STRENGTH.  None and no env: no grade, every file as before
         self.lut, self.grade, self.look, self.lut_strength = lut, grade, look, lut_strength
+        # sharpen: output sharpening -- "AMOUNT[,SIGMA[,THRESHOLD]]" (or a tuple of them): an exact integer unsharp mask applied on the GPU to
+        # every frame where the frames lie, in HBM, after width, enlargement, lens, shutter and grade -- the last thing done to the picture --
+        # and before the caption and the watermark, which are never sharpened (sharpen.py); AMOUNT above 0 and at most 4, SIGMA 0.3..8
+        # (default 1), THRESHOLD 0..255 (default 0); env KBE_SHARPEN.  None and no env: no sharpening, every file as before
+        self.sharpen = sharpen
         self.objectCommon = {'dblFocal': 1024.0 / 2, 'dblBaseline': 120}       # pipeline.py:26-27
         # The networks are four fifths of a video's time, and how fast MIOpen runs their convolutions depends on whether this
         # MACHINE has measured them before (measured, MI355X, profiles/r04_networks.txt): PyTorch's default (immediate) mode on a
@@ -171,7 +176,7 @@ class Pipeline():
     @torch.no_grad()
     def render(self, tensorImage, zoom_settings):
         """The clip's frames as a uint8 [steps,H,W,3] tensor in HBM, and nothing written: what _run renders, with the instance's width, lens,
-        shutter, grade and layers, up to process_kenburns(keep_on_device=True).  For callers that go on with the frames on the device (slideshow.py).  _run is kept
+        shutter, grade, sharpening and layers, up to process_kenburns(keep_on_device=True).  For callers that go on with the frames on the device (slideshow.py).  _run is kept
         byte for byte what it was, so its first half is repeated here: an option that _run learns has to be taught to this method as well
         (tests/test_transition_gpu.py holds the two to the same process_kenburns call)."""
         from .utils import miopen_tuned_once
@@ -195,6 +200,7 @@ class Pipeline():
             # (the layers' colour bytes in the frames' order: B, G, R, unless the caller fed R, G, B and says so in self.overlay_bgr)
             layers = layers_of(self, out_size or (lambda: (tensorImage.size(3), tensorImage.size(2))), bgr=getattr(self, 'overlay_bgr', True))
             graded = grade_of(self, bgr=getattr(self, 'overlay_bgr', True))
+            crisp = sharpen_of(self)
             with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
                 self.estimate(tensorImage)
                 lens = {}
@@ -202,11 +208,11 @@ class Pipeline():
                     from . import dof
                     aperture, near, far = lens_at
                     lens = {'lens': dof.Lens(dof.focus_depth(self.objectCommon['tensorRawDepth'], *near), dof.focus_depth(self.objectCommon['tensorRawDepth'], *far), aperture)}
-                return with_layers(layers, with_grade(graded, common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
+                return with_layers(layers, with_sharpen(crisp, with_grade(graded, common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
                                                 'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
                                                 'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=True,
                                                **({} if out_size is None else {'out_size': out_size}), **grow, **lens,
-                                               **({} if open_for is None else {'shutter': open_for}))))
+                                               **({} if open_for is None else {'shutter': open_for})))))
 
     def tuning_tag(self, width, height):
         """What MIOpen is tuned for, once per machine (utils.miopen_tuned_once): this pipeline's networks at this image size."""
@@ -254,6 +260,9 @@ class Pipeline():
         # KBE_LUT, KBE_GRADE, KBE_LOOK, KBE_LUT_STRENGTH (Pipeline(lut=, grade=, look=, lut_strength=), kbe.py --lut --grade --look): the file is
         # read and the table baked before any network runs too; the frames then stay in HBM, where they are graded before the layers go on
         graded = grade_of(self, bgr=not pretrained_estim)
+        # KBE_SHARPEN (Pipeline(sharpen=), kbe.py --sharpen): read and checked before any network runs too; the frames then stay in HBM, where
+        # they are sharpened after the grade and before the layers go on
+        crisp = sharpen_of(self)
         with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
             self.estimate(tensorImage)
             if inpaint_depth:
@@ -266,7 +275,7 @@ class Pipeline():
             jpeg_on_device = output_path is not None and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
             png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
             video_from_hbm = jpeg_on_device and (png_on_device or not self.output_frames)
-            on_device = png_on_device or video_from_hbm or gif_on or y4m_on or bool(layers) or graded is not None
+            on_device = png_on_device or video_from_hbm or gif_on or y4m_on or bool(layers) or graded is not None or crisp is not None
             lens = {}
             if lens_at is not None:
                 from . import dof
@@ -279,8 +288,9 @@ class Pipeline():
                                              **({} if open_for is None else {'shutter': open_for}))     # (without a width, a lens or a shutter the call is what it was)
         if on_device:
             with_grade(graded, frames)                                                  # the grade: in place, before the layers, which are never graded
+            with_sharpen(crisp, frames)                                                 # the sharpening: in place, the last thing done to the picture itself
             with_layers(layers, frames)                                                 # the caption, then the watermark: in place, before every output
-            if output_path is None:                                                     # (only with a grade or a layer: nothing is written)
+            if output_path is None:                                                     # (only with a grade, a sharpening or a layer: nothing is written)
                 host = frames.cpu().numpy()
                 return [host[i] for i in range(host.shape[0])]
             os.makedirs(output_path, exist_ok=True)
@@ -457,6 +467,21 @@ def grade_of(pipe, bgr=True):
     checked and baked here, on the host, before any network runs; None without one.  ValueError whose text begins with the option at fault."""
     from . import grade
     return grade.grade_for(grade.grade_request(*[getattr(pipe, name, None) for name in grade.OPTIONS]), bgr)
+
+
+def sharpen_of(pipe):
+    """The sharpening of a Pipeline (sharpen.request): what it was told, else the environment's KBE_SHARPEN -- read and checked on the host;
+    None without it."""
+    from . import sharpen
+    return sharpen.request(getattr(pipe, 'sharpen', None))
+
+
+def with_sharpen(request, frames):
+    """The frames, a uint8 [n,H,W,3] tensor in HBM, sharpened in place (sharpen.apply_sharpen); without a request they are returned as they are."""
+    if request is not None:
+        from . import sharpen
+        sharpen.apply_sharpen(frames, request)
+    return frames
 
 
 def with_grade(graded, frames):

@@ -18,6 +18,9 @@
                                                        (kbe.py's colour grading: every clip is graded on the GPU where Pipeline.render leaves it,
                                                         so transitions blend graded frames; the fade colour, the captions and the watermark are
                                                         not graded.  One grade for the whole show)
+        [--sharpen AMOUNT[,SIGMA[,THRESHOLD]]]         (kbe.py's output sharpening: every clip is sharpened on the GPU after its grade, before
+                                                        the clips are joined; the captions and the watermark are not sharpened.  One setting
+                                                        for the whole show)
         and of kbe.py's options: [--dolly] [--width N] [--enlarge] [--aperture A] [--focus U,V] [--focus-to U,V] [--shutter F] [--shutter-samples S]
         [--gif] [--gif-dither none|ordered] [--gif-width N] [--gif-fps F] [--y4m] [--write-frames] [--jpeg native|pillow|device]
         [--png native|device] [--inpaint-path P] [--refine-path P] [--estim-path P] [--inpaint-depth P] [--pretrained-refine]
@@ -193,6 +196,7 @@ def make(images, out_dir, pipe, transition_kind='dissolve', transition_frames=12
     bgr = not pretrained_estim                                      # (the frames are in the INPUT's channel order: B, G, R unless --pretrained-estim)
     titles, watermark = show_layers(show, layers, bgr)
     P.grade_of(pipe, bgr)                                           # (the clips' grade, which pipe.render applies: refused here, before a network runs)
+    P.sharpen_of(pipe)                                              # (... and their sharpening, which pipe.render applies after the grade)
     gif_on = out_dir is not None and bool(gif)
     if gif_on:
         gif_wide, gif_every = P.gif_shape(getattr(pipe, 'gif_width', None), getattr(pipe, 'gif_fps', None))
@@ -279,7 +283,8 @@ def main(argv=None):
                     semantics_path=cfg['semantics-path'], allow_random_weights=cfg['allow-random-weights'] or None, gif_dither=cfg['gif-dither'],
                     gif_width=cfg['gif-width'], gif_fps=cfg['gif-fps'], width=cfg['width'], aperture=cfg['aperture'], focus=cfg['focus'], focus_to=cfg['focus-to'],
                     shutter=cfg['shutter'], shutter_samples=cfg['shutter-samples'], steps=STEPS,
-                    **{name.replace('-', '_'): cfg[name] for name in kbe.GRADE_OPTIONS}, **({'enlarge': True} if cfg['enlarge'] else {}))
+                    **{name.replace('-', '_'): cfg[name] for name in kbe.GRADE_OPTIONS}, **({'enlarge': True} if cfg['enlarge'] else {}),
+                    **({} if cfg['sharpen'] is None else {'sharpen': cfg['sharpen']}))
     frames = make(images, cfg['out'], pipe, pretrained_estim=cfg['pretrained-estim'], gif=cfg['gif'], y4m=cfg['y4m'], names=cfg['in'], layers=cfg['layers'], **settings)
     print('%d frames of %dx%d from %d photos written to %s' % (len(frames), frames[0].shape[1], frames[0].shape[0], len(images), cfg['out']))
 
