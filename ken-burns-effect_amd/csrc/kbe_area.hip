@@ -7,7 +7,8 @@
 // and a row per step -- no 3-byte pixel is a byte-wide global load; the row's first pixel then lies 0..3 bytes into its LDS row.  Every thread
 // adds what the strip holds of its own footprint (exact integer sums: the order of the strips does not matter).  The tile's bytes are put
 // together in LDS at the output rows' own alignment modulo 16 and stored as 16-byte pieces, with dwords and single bytes only where a row's
-// ends do not fill a piece; nothing outside a row's 3 w bytes is written.
+// ends do not fill a piece; nothing outside a row's 3 w bytes is written.  The row fetch, the tile's row in LDS and its store are
+// kbe_rows.h's, which the other tile kernels share.
 //
 // Every loop has a static bound (the strips of the tile's span, the rows and pixels of a strip); no kernel waits for another workgroup.  A
 // thread walks its pixel's whole footprint, so the time per target pixel grows with (W / w)(H / h): meant for the few-fold reductions of
@@ -21,7 +22,7 @@ using namespace kbe_area;
 
 namespace {
 
-constexpr int kFramesPerLaunch = 12;                         // as the encoders' (kbe_units_scan.h)
+using kbe_rows::kFramesPerLaunch;
 constexpr int kTileX = 64, kTileY = 4;                      // one wave per target row of the tile
 constexpr int kStripRows = 16, kStripDwords = kBlock;       // a lane per dword of a strip's row
 constexpr int kStripPx = (4 * kStripDwords - 3) / 3;        // 340: 3 bytes of misalignment and 1020 of pixels fit the 1024
@@ -49,7 +50,7 @@ struct Strip {
     __device__ __forceinline__ const uint8_t* first(uint32_t sy) const { return src + (size_t) sy * stride + 3u * (size_t) x0; }
     __device__ __forceinline__ Row row(uint32_t sy) const
     {
-        return Row{bytes + (sy - y0) * (4u * kStripDwords) + (uint32_t) ((uintptr_t) first(sy) & 3u), x0};
+        return Row{bytes + (sy - y0) * (4u * kStripDwords) + kbe_rows::shift_of(first(sy)), x0};
     }
 };
 
@@ -79,9 +80,8 @@ __global__ __launch_bounds__(kBlock) void k_area_reduce(const AreaArgs a)
             __syncthreads();                                           // (the strip before this one has been read)
             for (uint32_t sy = y0; sy < y1; sy++) {
                 // the aligned dwords that hold a byte of pixels x0 .. x1 - 1 of row sy: every one of them holds a byte of the row
-                const uint8_t* const first = strip.first(sy);
-                const uint32_t shift = (uint32_t) ((uintptr_t) first & 3u), dwords = (shift + 3u * (x1 - x0) + 3u) >> 2;
-                if (tid < dwords) s_words[(sy - y0) * kStripDwords + tid] = reinterpret_cast<const uint32_t*>(first - shift)[tid];
+                const kbe_rows::Fetch row = kbe_rows::fetch_of(strip.first(sy), x1 - x0);
+                if (tid < row.dwords) s_words[(sy - y0) * kStripDwords + tid] = row.base[tid];
             }
             __syncthreads();
             accumulate(g, ox, oy, intersect(own, Window{x0, x1, y0, y1}), strip, acc);
@@ -89,32 +89,13 @@ __global__ __launch_bounds__(kBlock) void k_area_reduce(const AreaArgs a)
     }
 
     // the tile's bytes at their rows' alignment: row ty starts (its address mod 16) bytes into its LDS row
-    uint8_t* const dst = a.dst[blockIdx.z];
+    uint8_t* const row = a.dst[blockIdx.z] + (size_t) oy * a.out_stride + 3u * (size_t) ox0;
     if (mine) {
-        const uint32_t lead = (uint32_t) ((uintptr_t) (dst + (size_t) oy * a.out_stride + 3u * (size_t) ox0) & 15u);
+        const uint32_t lead = kbe_rows::lead_of(row);
         for (int c = 0; c < 3; c++) s_out[ty * kOutPitch + lead + 3u * tx + c] = rounded(acc[c], g);
     }
     __syncthreads();
-    if (ty < ny) {
-        uint8_t* const row = dst + (size_t) oy * a.out_stride + 3u * (size_t) ox0;
-        const uint32_t lead = (uint32_t) ((uintptr_t) row & 15u), end = lead + 3u * nx;           // the row's bytes are [lead, end) of the LDS row
-        const uint32_t at = 16u * tx;                                                              // lane tx takes the piece [at, at + 16)
-        if (at < end) {
-            const uint4 piece = *reinterpret_cast<const uint4*>(s_out + ty * kOutPitch + at);
-            uint8_t* const p = row - lead + at;                                                    // 16-byte aligned
-            const uint32_t lo = at < lead ? lead - at : 0u, hi = end - at < 16u ? end - at : 16u;
-            if (lo == 0u && hi == 16u) *reinterpret_cast<uint4*>(p) = piece;
-            else {
-                const uint32_t word[4] = {piece.x, piece.y, piece.z, piece.w};
-                for (uint32_t d = 0; d < 4u; d++) {
-                    if (lo <= 4u * d && 4u * d + 4u <= hi) reinterpret_cast<uint32_t*>(p)[d] = word[d];
-                    else
-                        for (uint32_t b = 4u * d; b < 4u * d + 4u; b++)
-                            if (lo <= b && b < hi) p[b] = (uint8_t) (word[d] >> (8u * (b & 3u)));
-                }
-            }
-        }
-    }
+    if (ty < ny) kbe_rows::store_tile_row(s_out + ty * kOutPitch, row, nx, 16u * tx);             // lane tx takes the piece [16 tx, 16 tx + 16)
 }
 
 }  // namespace
@@ -140,7 +121,7 @@ KBE_AREA_API int kbe_area_reduce_u8(const uint8_t* const* frames_u8, int n_frame
     else if (out_stride_bytes < 3 * w) what = "out_stride_bytes < 3 w";
     for (int i = 0; !what && i < n_frames; i++)
         if (!frames_u8[i] || !out_u8[i]) what = frames_u8[i] ? "null element of out_u8" : "null element of frames_u8";
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_area_reduce_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_area_reduce_u8", what);
 
     AreaArgs a;
     a.g = Shape{(uint32_t) W, (uint32_t) H, (uint32_t) w, (uint32_t) h};
@@ -148,11 +129,9 @@ KBE_AREA_API int kbe_area_reduce_u8(const uint8_t* const* frames_u8, int n_frame
     a.out_stride = (uint32_t) out_stride_bytes;
     const dim3 tiles(blocks_for((size_t) w, kTileX), blocks_for((size_t) h, kTileY));
     for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) {
-            a.src[i] = i < nf ? frames_u8[f0 + i] : nullptr;
-            a.dst[i] = i < nf ? out_u8[f0 + i] : nullptr;
-        }
+        const int nf = launch_frames(n_frames, f0, kFramesPerLaunch);
+        fill_slots(a.src, frames_u8, f0, nf);
+        fill_slots(a.dst, out_u8, f0, nf);
         hipLaunchKernelGGL(k_area_reduce, dim3(tiles.x, tiles.y, (unsigned) nf), dim3(kBlock), 0, (hipStream_t) stream, a);
     }
     return launched("kbe_area_reduce_u8");

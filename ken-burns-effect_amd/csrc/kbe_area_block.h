@@ -23,9 +23,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "kbe_rows.h"
+
 namespace kbe_area {
 
-constexpr int kMaxSide = 65535;
+using kbe_rows::kMaxSide;
 
 struct Shape {
     uint32_t W, H, w, h;

@@ -11,7 +11,8 @@
 //       step is skipped and (2) reads the staged raw rows.  The test is uniform over the launch;
 //   (2) every thread adds what the strip holds of its own footprint (exact integer sums: the order of the strips does not matter).
 // The tile's bytes are put together in LDS at the output rows' own alignment modulo 16 and stored as 16-byte pieces, with dwords and single
-// bytes only where a row's ends do not fill a piece; nothing outside a row's 3 w bytes is written.
+// bytes only where a row's ends do not fill a piece; nothing outside a row's 3 w bytes is written.  The row fetch, the tile's row in LDS
+// and its store are kbe_rows.h's, which k_area_reduce runs too.
 //
 // Every loop has a static bound (the strips of the tile's span, the rows and byte columns of a strip); no kernel waits for another
 // workgroup.  A thread walks its pixel's whole footprint, so the time per target pixel grows with (cw / w)(ch / h): meant for the few-fold
@@ -26,7 +27,7 @@ namespace kca = kbe_crop_area;
 
 namespace {
 
-constexpr int kFramesPerLaunch = 12;                         // as the encoders' (kbe_units_scan.h)
+using kbe_rows::kFramesPerLaunch;
 constexpr int kTileX = 64, kTileY = 4;                      // one wave per target row of the tile
 constexpr int kRawDwords = kBlock;                          // a lane per dword of a staged raw row
 constexpr int kRawPx = (4 * kRawDwords - 3) / 3;            // 340: 3 bytes of misalignment and 1020 of pixels fit the 1024
@@ -52,7 +53,7 @@ struct Raw {
     size_t stride;
     uint32_t rx0, ry0;
     __device__ __forceinline__ const uint8_t* first(uint32_t ry) const { return src + (size_t) ry * stride + 3u * (size_t) rx0; }
-    __device__ __forceinline__ const uint8_t* at(uint32_t ry) const { return bytes + (ry - ry0) * (4u * kRawDwords) + (uint32_t) ((uintptr_t) first(ry) & 3u); }
+    __device__ __forceinline__ const uint8_t* at(uint32_t ry) const { return bytes + (ry - ry0) * (4u * kRawDwords) + kbe_rows::shift_of(first(ry)); }
 };
 
 // the Sources of accumulate(): a strip of the patch from pixel (x0, y0) on -- made in LDS, or the staged raw rows themselves
@@ -109,9 +110,8 @@ __global__ __launch_bounds__(kBlock) void k_crop_area(const CropAreaArgs a)
             __syncthreads();                                           // (the strip before this one has been read)
             // (0) the aligned dwords that hold a byte of pixels rx0 .. rx1 - 1 of raw row ry: every one of them holds a byte of the row
             for (uint32_t ry = ry0; ry < ry1; ry++) {
-                const uint8_t* const first = raw.first(ry);
-                const uint32_t shift = (uint32_t) ((uintptr_t) first & 3u), dwords = (shift + 3u * (rx1 - rx0) + 3u) >> 2;
-                if (tid < dwords) s_words[(ry - ry0) * kRawDwords + tid] = reinterpret_cast<const uint32_t*>(first - shift)[tid];
+                const kbe_rows::Fetch row = kbe_rows::fetch_of(raw.first(ry), rx1 - rx0);
+                if (tid < row.dwords) s_words[(ry - ry0) * kRawDwords + tid] = row.base[tid];
             }
             __syncthreads();
             const Window in = intersect(own, Window{x0, x1, y0, y1});
@@ -151,32 +151,13 @@ __global__ __launch_bounds__(kBlock) void k_crop_area(const CropAreaArgs a)
     }
 
     // the tile's bytes at their rows' alignment: row ty starts (its address mod 16) bytes into its LDS row
-    uint8_t* const dst = a.dst[blockIdx.z];
+    uint8_t* const row = a.dst[blockIdx.z] + (size_t) oy * a.out_stride + 3u * (size_t) ox0;
     if (mine) {
-        const uint32_t lead = (uint32_t) ((uintptr_t) (dst + (size_t) oy * a.out_stride + 3u * (size_t) ox0) & 15u);
+        const uint32_t lead = kbe_rows::lead_of(row);
         for (int c = 0; c < 3; c++) s_out[ty * kOutPitch + lead + 3u * tx + c] = rounded(acc[c], g);
     }
     __syncthreads();
-    if (ty < ny) {
-        uint8_t* const row = dst + (size_t) oy * a.out_stride + 3u * (size_t) ox0;
-        const uint32_t lead = (uint32_t) ((uintptr_t) row & 15u), end = lead + 3u * nx;           // the row's bytes are [lead, end) of the LDS row
-        const uint32_t at = 16u * tx;                                                              // lane tx takes the piece [at, at + 16)
-        if (at < end) {
-            const uint4 piece = *reinterpret_cast<const uint4*>(s_out + ty * kOutPitch + at);
-            uint8_t* const p = row - lead + at;                                                    // 16-byte aligned
-            const uint32_t lo = at < lead ? lead - at : 0u, hi = end - at < 16u ? end - at : 16u;
-            if (lo == 0u && hi == 16u) *reinterpret_cast<uint4*>(p) = piece;
-            else {
-                const uint32_t word[4] = {piece.x, piece.y, piece.z, piece.w};
-                for (uint32_t d = 0; d < 4u; d++) {
-                    if (lo <= 4u * d && 4u * d + 4u <= hi) reinterpret_cast<uint32_t*>(p)[d] = word[d];
-                    else
-                        for (uint32_t b = 4u * d; b < 4u * d + 4u; b++)
-                            if (lo <= b && b < hi) p[b] = (uint8_t) (word[d] >> (8u * (b & 3u)));
-                }
-            }
-        }
-    }
+    if (ty < ny) kbe_rows::store_tile_row(s_out + ty * kOutPitch, row, nx, 16u * tx);             // lane tx takes the piece [16 tx, 16 tx + 16)
 }
 
 }  // namespace
@@ -204,7 +185,7 @@ KBE_CROP_AREA_API int kbe_crop_area_u8(const uint8_t* const* frames_u8, int n_fr
     else if (out_stride_bytes < 3 * w) what = "out_stride_bytes < 3 w";
     for (int i = 0; !what && i < n_frames; i++)
         if (!frames_u8[i] || !out_u8[i]) what = frames_u8[i] ? "null element of out_u8" : "null element of frames_u8";
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_crop_area_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_crop_area_u8", what);
 
     CropAreaArgs a;
     a.k = kca::Crop{(uint32_t) W, (uint32_t) H, (uint32_t) crop_w, (uint32_t) crop_h};
@@ -214,11 +195,9 @@ KBE_CROP_AREA_API int kbe_crop_area_u8(const uint8_t* const* frames_u8, int n_fr
     a.out_stride = (uint32_t) out_stride_bytes;
     const dim3 tiles(blocks_for((size_t) w, kTileX), blocks_for((size_t) h, kTileY));
     for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) {
-            a.src[i] = i < nf ? frames_u8[f0 + i] : nullptr;
-            a.dst[i] = i < nf ? out_u8[f0 + i] : nullptr;
-        }
+        const int nf = launch_frames(n_frames, f0, kFramesPerLaunch);
+        fill_slots(a.src, frames_u8, f0, nf);
+        fill_slots(a.dst, out_u8, f0, nf);
         hipLaunchKernelGGL(k_crop_area, dim3(tiles.x, tiles.y, (unsigned) nf), dim3(kBlock), 0, (hipStream_t) stream, a);
     }
     return launched("kbe_crop_area_u8");

@@ -32,7 +32,7 @@ struct Crop {
 
 KBE_AREA_HD bool shape_ok(int W, int H, int cw, int ch, int w, int h)
 {
-    return W >= 1 && H >= 1 && W <= kbe_area::kMaxSide && H <= kbe_area::kMaxSide && cw >= 1 && ch >= 1 && cw <= W && ch <= H && w >= 1 && h >= 1 && w <= cw && h <= ch;
+    return W >= 1 && H >= 1 && W <= kbe_rows::kMaxSide && H <= kbe_rows::kMaxSide && cw >= 1 && ch >= 1 && cw <= W && ch <= H && w >= 1 && h >= 1 && w <= cw && h <= ch;
 }
 
 // floor(c) of an axis, and whether c lies half a pixel beyond it

@@ -13,7 +13,8 @@
 //       the rest of the (2 R + 1)^2 window cannot contribute.  m is the same in the whole workgroup.  A tile of an in-focus region, and every
 //       tile at aperture 0, therefore costs a copy.
 // The tile's bytes are put together in LDS at the output rows' own alignment modulo 16 and stored as 16-byte pieces, with dwords and single
-// bytes only where a row's ends do not fill a piece; nothing outside a row's 3 W bytes is written (k_crop_area's rule).
+// bytes only where a row's ends do not fill a piece; nothing outside a row's 3 W bytes is written.  The row fetch's arithmetic, the tile's
+// row in LDS and its store are kbe_rows.h's, which k_area_reduce and k_crop_area run too.
 //
 // Every loop has a static bound (the rows and dwords of the staged window, at most 2 R + 1 steps per axis of the walk); no workgroup waits for
 // another.  LDS: 96 x 48 cells of 8 bytes (36 KiB, whatever R is) and 13.9 KiB of raw rows, which the output rows reuse: 51 144 bytes of a CU's
@@ -29,7 +30,7 @@ namespace kdof = kbe_dof;
 
 namespace {
 
-constexpr int kFramesPerLaunch = 12;                         // as the encoders' (kbe_units_scan.h)
+using kbe_rows::kFramesPerLaunch;
 constexpr int kTileX = 64, kTileY = 16;                     // one wave per target row of the tile
 constexpr int kThreads = kTileX * kTileY, kWaves = kThreads / 64;
 constexpr int kCellsX = kTileX + 2 * kdof::kMaxRadius, kCellsY = kTileY + 2 * kdof::kMaxRadius;      // 96 x 48 staged pixels
@@ -75,9 +76,8 @@ __global__ __launch_bounds__(kThreads) void k_dof(const DofArgs a)
     if (tid == 0u) s_max = 0u;
     // (0) the aligned dwords that hold a byte of pixels fx0 .. fx1 - 1 of row fy: every one of them holds a byte of the row
     for (uint32_t fy = fy0 + ty; fy < fy1; fy += kWaves) {
-        const uint8_t* const first = src + (size_t) fy * a.stride + 3u * (size_t) fx0;
-        const uint32_t shift = (uint32_t) ((uintptr_t) first & 3u), dwords = (shift + 3u * (fx1 - fx0) + 3u) >> 2;        // at most 73
-        for (uint32_t d = tx; d < dwords; d += 64u) s_raw[(fy - fy0) * kRawDwords + d] = reinterpret_cast<const uint32_t*>(first - shift)[d];
+        const kbe_rows::Fetch row = kbe_rows::fetch_of(src + (size_t) fy * a.stride + 3u * (size_t) fx0, fx1 - fx0);         // at most 73 dwords
+        for (uint32_t d = tx; d < row.dwords; d += 64u) s_raw[(fy - fy0) * kRawDwords + d] = row.base[d];
     }
     __syncthreads();
     // (1) the cells: a wave per row of the window
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void k_dof(const DofArgs a)
         const uint8_t* raw_row = nullptr;
         if (row_in) {
             const uint8_t* const first = src + (size_t) y * a.stride + 3u * (size_t) fx0;
-            raw_row = reinterpret_cast<const uint8_t*>(s_raw + ((uint32_t) y - fy0) * kRawDwords) + (uint32_t) ((uintptr_t) first & 3u);
+            raw_row = reinterpret_cast<const uint8_t*>(s_raw + ((uint32_t) y - fy0) * kRawDwords) + kbe_rows::shift_of(first);
         }
         for (int lx = (int) tx; lx < wx; lx += 64) {
             const int x = px0 + lx;
@@ -109,6 +109,7 @@ __global__ __launch_bounds__(kThreads) void k_dof(const DofArgs a)
     __syncthreads();
     // (2)
     const int m = (int) s_max;
+    uint8_t* const row = a.dst[blockIdx.z] + (size_t) (oy0 + ty) * a.out_stride + 3u * (size_t) ox0;         // the output row of this thread's wave
     if (mine) {
         const int cell = ((int) ty + R) * kCellsX + (int) tx + R;
         const uint32_t own = s_px[cell], rp = own >> 24;
@@ -126,30 +127,11 @@ __global__ __launch_bounds__(kThreads) void k_dof(const DofArgs a)
             }
         }
         // the tile's bytes at their rows' alignment: row ty starts (its address mod 16) bytes into its LDS row (the raw rows are done with)
-        const uint32_t lead = (uint32_t) ((uintptr_t) (a.dst[blockIdx.z] + (size_t) (oy0 + ty) * a.out_stride + 3u * (size_t) ox0) & 15u);
+        const uint32_t lead = kbe_rows::lead_of(row);
         for (int c = 0; c < 3; c++) s_out[ty * kOutPitch + lead + 3u * tx + c] = (uint8_t) kdof::rounded(s.v[c], s.w);
     }
     __syncthreads();
-    if (ty < ny) {
-        uint8_t* const row = a.dst[blockIdx.z] + (size_t) (oy0 + ty) * a.out_stride + 3u * (size_t) ox0;
-        const uint32_t lead = (uint32_t) ((uintptr_t) row & 15u), end = lead + 3u * nx;           // the row's bytes are [lead, end) of the LDS row
-        const uint32_t at = 16u * tx;                                                              // lane tx takes the piece [at, at + 16)
-        if (at < end) {
-            const uint4 piece = *reinterpret_cast<const uint4*>(s_out + ty * kOutPitch + at);
-            uint8_t* const p = row - lead + at;                                                    // 16-byte aligned
-            const uint32_t lo = at < lead ? lead - at : 0u, hi = end - at < 16u ? end - at : 16u;
-            if (lo == 0u && hi == 16u) *reinterpret_cast<uint4*>(p) = piece;
-            else {
-                const uint32_t word[4] = {piece.x, piece.y, piece.z, piece.w};
-                for (uint32_t d = 0; d < 4u; d++) {
-                    if (lo <= 4u * d && 4u * d + 4u <= hi) reinterpret_cast<uint32_t*>(p)[d] = word[d];
-                    else
-                        for (uint32_t b = 4u * d; b < 4u * d + 4u; b++)
-                            if (lo <= b && b < hi) p[b] = (uint8_t) (word[d] >> (8u * (b & 3u)));
-                }
-            }
-        }
-    }
+    if (ty < ny) kbe_rows::store_tile_row(s_out + ty * kOutPitch, row, nx, 16u * tx);             // lane tx takes the piece [16 tx, 16 tx + 16)
 }
 
 }  // namespace
@@ -185,19 +167,12 @@ KBE_DOF_API int kbe_dof_u8(const uint8_t* const* frames_u8, const float* const* 
     }
     // a gather in place is wrong: no output may share a byte with a source frame or a depth plane of the call
     if (!what) {
-        const uintptr_t src_bytes = (uintptr_t) (H - 1) * (uintptr_t) stride_bytes + 3u * (uintptr_t) W;
-        const uintptr_t depth_bytes = 4u * ((uintptr_t) (H - 1) * (uintptr_t) depth_stride_floats + (uintptr_t) W);
-        const uintptr_t out_bytes = (uintptr_t) (H - 1) * (uintptr_t) out_stride_bytes + 3u * (uintptr_t) W;
-        for (int i = 0; !what && i < n_frames; i++) {
-            const uintptr_t o0 = (uintptr_t) out_u8[i], o1 = o0 + out_bytes;
-            for (int j = 0; !what && j < n_frames; j++) {
-                const uintptr_t s0 = (uintptr_t) frames_u8[j], d0 = (uintptr_t) depth_f32[j];
-                if (o0 < s0 + src_bytes && s0 < o1) what = "an element of out_u8 overlaps a source frame";
-                else if (o0 < d0 + depth_bytes && d0 < o1) what = "an element of out_u8 overlaps a depth plane";
-            }
-        }
+        const uintptr_t src_bytes = frame_extent(H, stride_bytes, 3u * (uintptr_t) W), out_bytes = frame_extent(H, out_stride_bytes, 3u * (uintptr_t) W);
+        const uintptr_t depth_bytes = frame_extent(H, 4u * (uintptr_t) depth_stride_floats, 4u * (uintptr_t) W);
+        if (any_overlap(out_u8, n_frames, out_bytes, frames_u8, n_frames, src_bytes)) what = "an element of out_u8 overlaps a source frame";
+        else if (any_overlap(out_u8, n_frames, out_bytes, depth_f32, n_frames, depth_bytes)) what = "an element of out_u8 overlaps a depth plane";
     }
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_dof_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_dof_u8", what);
 
     DofArgs a;
     a.aperture = (float) aperture;
@@ -209,13 +184,11 @@ KBE_DOF_API int kbe_dof_u8(const uint8_t* const* frames_u8, const float* const* 
     a.out_stride = (uint32_t) out_stride_bytes;
     const dim3 tiles(blocks_for((size_t) W, kTileX), blocks_for((size_t) H, kTileY));
     for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) {
-            a.src[i] = i < nf ? frames_u8[f0 + i] : nullptr;
-            a.depth[i] = i < nf ? depth_f32[f0 + i] : nullptr;
-            a.dst[i] = i < nf ? out_u8[f0 + i] : nullptr;
-            a.focus[i] = i < nf ? (float) focus[f0 + i] : 1.0f;
-        }
+        const int nf = launch_frames(n_frames, f0, kFramesPerLaunch);
+        fill_slots(a.src, frames_u8, f0, nf);
+        fill_slots(a.depth, depth_f32, f0, nf);
+        fill_slots(a.dst, out_u8, f0, nf);
+        for (int i = 0; i < kFramesPerLaunch; i++) a.focus[i] = i < nf ? (float) focus[f0 + i] : 1.0f;
         hipLaunchKernelGGL(k_dof, dim3(tiles.x, tiles.y, (unsigned) nf), dim3(kThreads), 0, (hipStream_t) stream, a);
     }
     return launched("kbe_dof_u8");

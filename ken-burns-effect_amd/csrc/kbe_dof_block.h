@@ -34,10 +34,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "kbe_rows.h"
+
 namespace kbe_dof {
 
+using kbe_rows::kMaxSide;
+
 constexpr int kMaxRadius = 16;
-constexpr int kMaxSide = 65535;
 constexpr uint32_t kUnit = 8192u;                       // kWeight[0]: the weight of a pixel that is in focus
 
 // n(e): the lattice points of the closed disc of radius e, by counting

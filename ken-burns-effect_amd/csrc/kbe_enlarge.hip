@@ -14,6 +14,7 @@
 //   (4) the pass down the columns out of that plane, into the tile's bytes in LDS at the output rows' own alignment modulo 16;
 //   (5) the rows are stored as 16-byte pieces, with dwords and single bytes only where a row's ends do not fill a piece; nothing outside a
 //       row's 3 w bytes is written.
+// The row fetch's arithmetic in (1), the tile's row in LDS in (4) and its store in (5) are kbe_rows.h's, which the other tile kernels run too.
 // A tile is 16 rows high so that (3), which runs once per row of the span, is shared by many output rows.  Every loop has a static bound;
 // no workgroup waits for another; there are no tables in device memory.
 #include "kbe_enlarge.h"
@@ -26,7 +27,7 @@ namespace ken = kbe_enlarge;
 
 namespace {
 
-constexpr int kFramesPerLaunch = 12;                         // as the encoders' (kbe_units_scan.h)
+using kbe_rows::kFramesPerLaunch;
 constexpr int kTileX = 64, kTileY = 16;
 // n target indices in a row lie within ceil((n - 1) n_in / n_out) <= n - 1 values of i, and the taps are i - 1 .. i + 2
 constexpr int kSpanPx = kTileX + 3, kSpanRows = kTileY + 3;
@@ -87,14 +88,13 @@ __global__ __launch_bounds__(kBlock) void k_enlarge(const EnlargeArgs a)
     for (int trip = 0; trip < kStageTrips; trip++) {
         const uint32_t at = tid + (uint32_t) trip * kBlock, row = at / kRawDwords, d = at - row * kRawDwords;
         if (row >= ry1 - ry0) break;
-        const uint8_t* const first = src + (size_t) (ry0 + row) * a.stride + 3u * (size_t) rx0;
-        const uint32_t shift = (uint32_t) ((uintptr_t) first & 3u), dwords = (shift + 3u * (rx1 - rx0) + 3u) >> 2;
-        if (d < dwords) s_words[at] = reinterpret_cast<const uint32_t*>(first - shift)[d];
+        const kbe_rows::Fetch raw = kbe_rows::fetch_of(src + (size_t) (ry0 + row) * a.stride + 3u * (size_t) rx0, rx1 - rx0);
+        if (d < raw.dwords) s_words[at] = raw.base[d];
     }
     __syncthreads();
     // raw row ry, from its pixel rx0 on, starts (its address mod 4) bytes into LDS row ry - ry0
     auto raw_row = [&](uint32_t ry) -> const uint8_t* {
-        return s_raw + (ry - ry0) * (4u * kRawDwords) + (uint32_t) ((uintptr_t) (src + (size_t) ry * a.stride + 3u * (size_t) rx0) & 3u);
+        return s_raw + (ry - ry0) * (4u * kRawDwords) + kbe_rows::shift_of(src + (size_t) ry * a.stride + 3u * (size_t) rx0);
     };
     // (2) the span's patch bytes: byte column b is channel b % 3 of patch pixel px0 + b / 3; a thread owns one and walks down the rows
     if (!whole) {
@@ -128,31 +128,13 @@ __global__ __launch_bounds__(kBlock) void k_enlarge(const EnlargeArgs a)
         if (ty >= ny) break;
         if (b >= 3u * nx) continue;
         const ken::Taps& t = s_taps[kTileX + ty];
-        const uint32_t lead = (uint32_t) ((uintptr_t) (dst + (size_t) (oy0 + ty) * a.out_stride + 3u * (size_t) ox0) & 15u);
+        const uint32_t lead = kbe_rows::lead_of(dst + (size_t) (oy0 + ty) * a.out_stride + 3u * (size_t) ox0);
         s_out[ty * kOutPitch + lead + b] = (uint8_t) ken::pass(t.c, s_plane[t.t[0] * kPlanePitch + b], s_plane[t.t[1] * kPlanePitch + b], s_plane[t.t[2] * kPlanePitch + b], s_plane[t.t[3] * kPlanePitch + b]);
     }
     __syncthreads();
     // (5) sixteen lanes per row of the tile, lane `piece` of them takes the bytes [16 piece, 16 piece + 16) of the LDS row
     const uint32_t ty = tid / 16u, at = 16u * (tid & 15u);
-    if (ty < ny) {
-        uint8_t* const row = dst + (size_t) (oy0 + ty) * a.out_stride + 3u * (size_t) ox0;
-        const uint32_t lead = (uint32_t) ((uintptr_t) row & 15u), end = lead + 3u * nx;           // the row's bytes are [lead, end) of the LDS row
-        if (at < end) {
-            const uint4 piece = *reinterpret_cast<const uint4*>(s_out + ty * kOutPitch + at);
-            uint8_t* const p = row - lead + at;                                                    // 16-byte aligned
-            const uint32_t lo = at < lead ? lead - at : 0u, hi = end - at < 16u ? end - at : 16u;
-            if (lo == 0u && hi == 16u) *reinterpret_cast<uint4*>(p) = piece;
-            else {
-                const uint32_t word[4] = {piece.x, piece.y, piece.z, piece.w};
-                for (uint32_t d = 0; d < 4u; d++) {
-                    if (lo <= 4u * d && 4u * d + 4u <= hi) reinterpret_cast<uint32_t*>(p)[d] = word[d];
-                    else
-                        for (uint32_t b = 4u * d; b < 4u * d + 4u; b++)
-                            if (lo <= b && b < hi) p[b] = (uint8_t) (word[d] >> (8u * (b & 3u)));
-                }
-            }
-        }
-    }
+    if (ty < ny) kbe_rows::store_tile_row(s_out + ty * kOutPitch, dst + (size_t) (oy0 + ty) * a.out_stride + 3u * (size_t) ox0, nx, at);
 }
 
 }  // namespace
@@ -171,7 +153,7 @@ KBE_ENLARGE_API int kbe_enlarge_u8(const uint8_t* const* frames_u8, int n_frames
     if (!frames_u8) what = "null frames_u8";
     else if (!out_u8) what = "null out_u8";
     else if (n_frames < 1) what = "n_frames < 1";
-    else if (!(W >= 1 && W <= kbe_area::kMaxSide && H >= 1 && H <= kbe_area::kMaxSide)) what = "W or H outside 1..65535";
+    else if (!(W >= 1 && W <= kbe_rows::kMaxSide && H >= 1 && H <= kbe_rows::kMaxSide)) what = "W or H outside 1..65535";
     else if (!(crop_w >= 1 && crop_w <= W)) what = "crop_w outside 1..W";
     else if (!(crop_h >= 1 && crop_h <= H)) what = "crop_h outside 1..H";
     else if (!(w >= crop_w && w <= ken::kMaxOut)) what = "w outside crop_w..16384: the entry only enlarges";
@@ -180,7 +162,7 @@ KBE_ENLARGE_API int kbe_enlarge_u8(const uint8_t* const* frames_u8, int n_frames
     else if (out_stride_bytes < 3 * w) what = "out_stride_bytes < 3 w";
     for (int i = 0; !what && i < n_frames; i++)
         if (!frames_u8[i] || !out_u8[i]) what = frames_u8[i] ? "null element of out_u8" : "null element of frames_u8";
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_enlarge_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_enlarge_u8", what);
 
     EnlargeArgs a;
     a.k = kca::Crop{(uint32_t) W, (uint32_t) H, (uint32_t) crop_w, (uint32_t) crop_h};
@@ -190,11 +172,9 @@ KBE_ENLARGE_API int kbe_enlarge_u8(const uint8_t* const* frames_u8, int n_frames
     a.out_stride = (uint32_t) out_stride_bytes;
     const dim3 tiles(blocks_for((size_t) w, kTileX), blocks_for((size_t) h, kTileY));
     for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) {
-            a.src[i] = i < nf ? frames_u8[f0 + i] : nullptr;
-            a.dst[i] = i < nf ? out_u8[f0 + i] : nullptr;
-        }
+        const int nf = launch_frames(n_frames, f0, kFramesPerLaunch);
+        fill_slots(a.src, frames_u8, f0, nf);
+        fill_slots(a.dst, out_u8, f0, nf);
         hipLaunchKernelGGL(k_enlarge, dim3(tiles.x, tiles.y, (unsigned) nf), dim3(kBlock), 0, (hipStream_t) stream, a);
     }
     return launched("kbe_enlarge_u8");

@@ -30,7 +30,7 @@ constexpr int kOneBits = 14, kOne = 1 << kOneBits;
 
 KBE_AREA_HD bool shape_ok(int W, int H, int cw, int ch, int w, int h)
 {
-    return W >= 1 && H >= 1 && W <= kbe_area::kMaxSide && H <= kbe_area::kMaxSide && cw >= 1 && ch >= 1 && cw <= W && ch <= H && w >= cw && h >= ch && w <= kMaxOut && h <= kMaxOut;
+    return W >= 1 && H >= 1 && W <= kbe_rows::kMaxSide && H <= kbe_rows::kMaxSide && cw >= 1 && ch >= 1 && cw <= W && ch <= H && w >= cw && h >= ch && w <= kMaxOut && h <= kMaxOut;
 }
 
 // floor(a / b), b > 0

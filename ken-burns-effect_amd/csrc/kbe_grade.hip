@@ -33,15 +33,10 @@ constexpr int kFramesPerLaunch = KBE_GRADE_FRAMES_PER_LAUNCH;
 constexpr int kLanes = 64;
 constexpr int kSpanPixels = kLanes * kgr::kRunPixels;       // 1024: the pixels of a row that one wave takes in one trip
 constexpr int kCUs = 256;                                   // of the MI355X: what caps the grid
-static_assert(kSpanPixels == 1024 && kFramesPerLaunch == 12 && kgr::kRunBytes == 48, "the kernel's layout");
+static_assert(kSpanPixels == 1024 && kFramesPerLaunch == kbe_rows::kFramesPerLaunch && kgr::kRunBytes == 48, "the kernel's layout");
 
-// aligned dwords, loaded and stored as one piece at the alignment of a dword
-struct __attribute__((packed, aligned(4))) Dwords4 {
-    uint32_t x, y, z, w;
-};
-struct __attribute__((packed, aligned(4))) Dwords3 {
-    uint32_t x, y, z;
-};
+using kbe_rows::Dwords3;
+using kbe_rows::Dwords4;
 
 struct GradeArgs {
     uint8_t* frame[kFramesPerLaunch];
@@ -133,15 +128,6 @@ __global__ __launch_bounds__(kThreads) void k_grade(const GradeArgs a)
     }
 }
 
-struct Range {
-    uintptr_t first, end;
-};
-
-bool intersect(const Range& a, const Range& b)
-{
-    return a.first < b.end && b.first < a.end;
-}
-
 // One launch of the kernel whose LDS holds kNodes^3 dwords, with workgroups of kThreads of which a CU holds kPerCU
 template <int kNodes, int kThreads, int kPerCU>
 void launch_class(GradeArgs& a, hipStream_t stream)
@@ -178,16 +164,11 @@ KBE_GRADE_API int kbe_grade_u8(uint8_t* const* frames_u8, int n, int W, int H, i
     }
     // a lane reads and writes its frame's bytes and the workgroups read the table's: a frame may share no byte with another frame of the call, nor with the table
     if (!what) {
-        const uintptr_t frame_bytes = (uintptr_t) (H - 1) * (uintptr_t) stride_bytes + 3u * (uintptr_t) W;
-        const Range table = {(uintptr_t) lut, (uintptr_t) lut + 4u * (uintptr_t) (N * N * N)};
-        for (int i = 0; !what && i < n; i++) {
-            const Range mine = {(uintptr_t) frames_u8[i], (uintptr_t) frames_u8[i] + frame_bytes};
-            if (intersect(mine, table)) what = "an element of frames_u8 overlaps the table";
-            for (int j = i + 1; !what && j < n; j++)
-                if (intersect(mine, Range{(uintptr_t) frames_u8[j], (uintptr_t) frames_u8[j] + frame_bytes})) what = "an element of frames_u8 overlaps another frame";
-        }
+        const uintptr_t frame_bytes = frame_extent(H, stride_bytes, 3u * (uintptr_t) W);
+        if (any_overlap(frames_u8, n, frame_bytes, &lut, 1, 4u * (uintptr_t) (N * N * N))) what = "an element of frames_u8 overlaps the table";
+        else if (any_two_overlap(frames_u8, n, frame_bytes)) what = "an element of frames_u8 overlaps another frame";
     }
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_grade_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_grade_u8", what);
 
     GradeArgs a;
     a.lut = lut;

@@ -51,9 +51,9 @@
 
 namespace kbe_grade {
 
-using kbe_shutter::align_bytes;
+using kbe_rows::align_bytes;
+using kbe_rows::kMaxSide;
 
-constexpr int kMaxSide = 65535;
 constexpr int kMinNodes = 2;
 constexpr int kMaxNodes = 33;
 constexpr int kMaxStrength = 256;
@@ -207,9 +207,9 @@ KBE_GRADE_HD void grade_run(uint32_t c[kRunDwords], const uint32_t* lut, uint32_
 }
 
 // A run that begins b = 1..3 bytes into an aligned dword lies in 13 aligned dwords x[0..12], its bytes the bytes [b, b + 48) of them.
-KBE_GRADE_HD void run_from_aligned(const uint32_t x[kRunDwords + 1], uint32_t b, uint32_t c[kRunDwords])
+KBE_GRADE_HD void run_from_aligned(const uint32_t (&x)[kRunDwords + 1], uint32_t b, uint32_t (&c)[kRunDwords])
 {
-    for (int k = 0; k < kRunDwords; k++) c[k] = align_bytes(x[k + 1], x[k], b);
+    kbe_rows::realign<kRunDwords>(x, b, c);
 }
 
 // ... and back: the bytes of x[0] before the run and of x[12] behind it are 0

@@ -27,12 +27,14 @@
 
 namespace kbe_overlay {
 
-using kbe_shutter::align_bytes;
+using kbe_rows::align_bytes;
+using kbe_rows::frame_dword_holds_a_byte;
+using kbe_rows::kMaxSide;
+using kbe_rows::kPiece;                       // bytes of a frame: what one lane of the kernel loads, composites and stores
+using kbe_rows::realign;                      // (the six overlay pixels, 24 bytes that start b bytes into the 28 bytes x[0..6])
 using kbe_shutter::mul_hi;
 
-constexpr int kMaxSide = 65535;
 constexpr int kMaxOpacity = 256;
-constexpr int kPiece = 16;                    // bytes of a frame: what one lane of the kernel loads, composites and stores
 constexpr int kPixels = 6;                    // the pixels that hold a piece's bytes
 
 // -- the plain forms ---------------------------------------------------------------------------
@@ -110,12 +112,6 @@ KBE_OVERLAY_HD bool all_overlay_dwords_hold_a_byte(int32_t x0, int32_t pixels)
     return x0 >= 0 && x0 + kPixels < pixels;
 }
 
-// the 24 bytes that start b bytes into the 28 bytes x[0..6]: a funnel shift by bytes.  With b = 0 nothing of x[6] is read
-KBE_OVERLAY_HD void realign(const uint32_t x[7], uint32_t b, uint32_t pixel[6])
-{
-    for (int k = 0; k < kPixels; k++) pixel[k] = align_bytes(x[k + 1], x[k], b);
-}
-
 // bytes 0..2 of six dwords as a stream of 18 bytes, those of dword k at byte 3 k (the last two bytes of s[4] are 0)
 KBE_OVERLAY_HD void colour_stream(const uint32_t p[6], uint32_t s[5])
 {
@@ -143,47 +139,41 @@ KBE_OVERLAY_HD uint32_t over_piece(const uint32_t pixel[6], uint32_t opacity, ui
     return any;
 }
 
-// which of a piece's four frame dwords hold a byte of the rectangle's row, whose bytes are [lo, hi) of the piece
-KBE_OVERLAY_HD bool frame_dword_holds_a_byte(uint32_t d, uint32_t lo, uint32_t hi)
-{
-    return 4u * d < hi && 4u * d + 4u > lo;
-}
-
 #if !defined(__HIPCC__)
 // One row of the clipped rectangle on a CPU, serially and in place, the way the kernel takes it: pieces of 16 bytes at the alignment of the
 // frame's bytes (`lead` = the address of the row's first byte modulo 16, given by the caller so that a test can walk through all sixteen),
 // the overlay's pixels realigned by their address modulo 4 (overlay_class: the address of the row's first overlay pixel, any number
 // congruent to it modulo 4).  The aligned dwords are put together byte by byte from the rows alone -- 0 where a row has no byte or the
-// dword is not loaded --, so nothing outside the rows is read; a piece whose e are all 0 is not written.
+// dword is not loaded --, so nothing outside the rows is read; a piece whose e are all 0 is not written.  The walk over the pieces, a
+// piece's bounds and its store are kbe_rows.h's.
 inline void over_row(uint8_t* frame, const uint8_t* overlay, uint32_t overlay_class, int32_t pixels, uint32_t opacity, uint32_t lead)
 {
     const long row_bytes = 3l * pixels;
-    for (long at = 0; at < (long) lead + row_bytes; at += kPiece) {
-        const long j0 = at - (long) lead;
-        const uint32_t lo = j0 < 0 ? (uint32_t) -j0 : 0u, hi = row_bytes - j0 < 16 ? (uint32_t) (row_bytes - j0) : 16u;
+    kbe_rows::for_each_piece(row_bytes, lead, [&](uint32_t at) {
+        const long j0 = (long) at - (long) lead;
+        const kbe_rows::Piece q = kbe_rows::piece_of(frame, lead, lead + (uint32_t) row_bytes, at);
         int32_t x0;
         uint32_t r;
         first_pixel(j0, &x0, &r);
         const uint32_t b = (uint32_t) (((long) overlay_class + 4l * x0) & 3);
         const bool all = all_overlay_dwords_hold_a_byte(x0, pixels);
-        uint8_t bytes[28], mine[16], piece[16];
+        uint8_t bytes[28], mine[16];
         for (long i = 0; i < 28; i++) {
             const long j = 4l * x0 - (long) b + i;                               // as a byte of the overlay's row
             const bool loaded = all || overlay_dword_holds_a_byte(x0, b, (int) (i / 4), pixels);
             bytes[i] = loaded && j >= 0 && j < 4l * pixels ? overlay[j] : (uint8_t) 0;
         }
         for (long i = 0; i < 16; i++) {
-            const bool loaded = (lo == 0u && hi == 16u) || frame_dword_holds_a_byte((uint32_t) (i / 4), lo, hi);
+            const bool loaded = q.whole() || frame_dword_holds_a_byte((uint32_t) (i / 4), q.lo, q.hi);
             mine[i] = loaded && j0 + i >= 0 && j0 + i < row_bytes ? frame[j0 + i] : (uint8_t) 0;
         }
         uint32_t x[7], pixel[6], c[4], word[4];
         memcpy(x, bytes, 28);
         memcpy(c, mine, 16);
         realign(x, b, pixel);
-        if (over_piece(pixel, opacity, r, c, word) == 0u) continue;
-        memcpy(piece, word, 16);
-        for (uint32_t i = lo; i < hi; i++) frame[j0 + i] = piece[i];
-    }
+        if (over_piece(pixel, opacity, r, c, word) == 0u) return;
+        kbe_rows::store_piece(frame, lead, lead + (uint32_t) row_bytes, at, word);
+    });
 }
 #endif
 

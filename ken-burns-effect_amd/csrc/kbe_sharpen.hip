@@ -12,6 +12,7 @@
 //       tile's bytes in LDS at the output rows' own alignment modulo 16;
 //   (4) the rows are stored as 16-byte pieces, with dwords and single bytes only where a row's ends do not fill a piece; nothing outside
 //       a row's 3 W bytes is written.
+// The row fetch's arithmetic in (1), the tile's row in LDS in (3) and its store in (4) are kbe_rows.h's, which the other tile kernels run too.
 // The tile is 64 x 32: (2) runs once per staged row, 32 + 2 R of them for 32 rows of output -- 2.5 times over at R = 24, where a tile 16
 // rows high would take 4 -- and the LDS a workgroup asks for follows R (lds_bytes): 26 784 bytes at R = 1, 29 616 at R = 3, 65 216 at R = 24,
 // so that at the radii of everyday sigmas five workgroups share a CU's 160 KiB, and two at R = 24.  The taps travel in the kernel's arguments.  Every loop has
@@ -25,7 +26,7 @@ namespace ksh = kbe_sharpen;
 
 namespace {
 
-constexpr int kFramesPerLaunch = 12;                         // as the encoders' (kbe_units_scan.h)
+using kbe_rows::kFramesPerLaunch;
 constexpr int kTileX = 64, kTileY = 32;
 constexpr int kRowBytes = 3 * kTileX;                        // 192: a row of the tile, and of the plane, in values
 constexpr int kOutPitch = kRowBytes + 16;                    // a tile's row of 192 bytes, 0..15 bytes into its LDS row
@@ -74,16 +75,15 @@ __global__ __launch_bounds__(kBlock) void k_sharpen(const SharpenArgs a)
     const uint8_t* const src = a.src[blockIdx.z];
     auto frame_row = [&](uint32_t r) -> const uint8_t* { return src + (size_t) ksh::clamped((int32_t) (y0 + r) - R, a.H) * a.stride + 3u * (size_t) fx; };
     // pixel fx of staged row r in LDS: (its address mod 4) bytes into the row's first dword
-    auto staged = [&](uint32_t r) -> uint8_t* { return s_raw + r * pitch + lead_in + (uint32_t) ((uintptr_t) frame_row(r) & 3u); };
+    auto staged = [&](uint32_t r) -> uint8_t* { return s_raw + r * pitch + lead_in + kbe_rows::shift_of(frame_row(r)); };
 
     // (1) the aligned dwords that hold a byte of the pixels [fx, lx) of a row: every one of them holds a byte of the row
     const uint32_t pitch_dwords = pitch / 4u;
     for (int trip = 0; trip < kStageTrips; trip++) {
         const uint32_t at = tid + (uint32_t) trip * kBlock, r = at / pitch_dwords, d = at - r * pitch_dwords;
         if (r >= n_rows) break;
-        const uint8_t* const first = frame_row(r);
-        const uint32_t shift = (uint32_t) ((uintptr_t) first & 3u), dwords = (shift + 3u * span + 3u) >> 2;
-        if (d < dwords) s_words[(r * pitch + lead_in) / 4u + d] = reinterpret_cast<const uint32_t*>(first - shift)[d];
+        const kbe_rows::Fetch raw = kbe_rows::fetch_of(frame_row(r), span);
+        if (d < raw.dwords) s_words[(r * pitch + lead_in) / 4u + d] = raw.base[d];
     }
     __syncthreads();
     // (1b) the same for every lane of the workgroup: only a tile at the frame's left or right border has such pixels
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void k_sharpen(const SharpenArgs a)
         if (b >= 3u * nx) continue;
         const uint16_t* const p = s_plane + (ty + (uint32_t) R) * kRowBytes + b;
         const uint32_t b16 = ksh::column_pass(a.taps, [&](int k) { return (uint32_t) p[k * kRowBytes]; });
-        const uint32_t lead = (uint32_t) ((uintptr_t) (dst + (size_t) (y0 + ty) * a.out_stride + 3u * (size_t) x0) & 15u);
+        const uint32_t lead = kbe_rows::lead_of(dst + (size_t) (y0 + ty) * a.out_stride + 3u * (size_t) x0);
         s_out[ty * kOutPitch + lead + b] = (uint8_t) ksh::sharpened(staged(ty + (uint32_t) R)[centre + b], b16, a.amount, a.threshold);
     }
     __syncthreads();
@@ -125,22 +125,7 @@ __global__ __launch_bounds__(kBlock) void k_sharpen(const SharpenArgs a)
     for (int trip = 0; trip < kStoreTrips; trip++) {
         const uint32_t ty = (tid + (uint32_t) trip * kBlock) / 16u, at = 16u * (tid & 15u);
         if (ty >= ny) break;
-        uint8_t* const row = dst + (size_t) (y0 + ty) * a.out_stride + 3u * (size_t) x0;
-        const uint32_t lead = (uint32_t) ((uintptr_t) row & 15u), end = lead + 3u * nx;           // the row's bytes are [lead, end) of the LDS row
-        if (at >= end) continue;
-        const uint4 piece = *reinterpret_cast<const uint4*>(s_out + ty * kOutPitch + at);
-        uint8_t* const p = row - lead + at;                                                    // 16-byte aligned
-        const uint32_t lo = at < lead ? lead - at : 0u, hi = end - at < 16u ? end - at : 16u;
-        if (lo == 0u && hi == 16u) *reinterpret_cast<uint4*>(p) = piece;
-        else {
-            const uint32_t word[4] = {piece.x, piece.y, piece.z, piece.w};
-            for (uint32_t d = 0; d < 4u; d++) {
-                if (lo <= 4u * d && 4u * d + 4u <= hi) reinterpret_cast<uint32_t*>(p)[d] = word[d];
-                else
-                    for (uint32_t b = 4u * d; b < 4u * d + 4u; b++)
-                        if (lo <= b && b < hi) p[b] = (uint8_t) (word[d] >> (8u * (b & 3u)));
-            }
-        }
+        kbe_rows::store_tile_row(s_out + ty * kOutPitch, dst + (size_t) (y0 + ty) * a.out_stride + 3u * (size_t) x0, nx, at);
     }
 }
 
@@ -161,7 +146,7 @@ KBE_SHARPEN_API int kbe_sharpen_u8(const uint8_t* const* frames_u8, int n_frames
     else if (!out_u8) what = "null out_u8";
     else if (!taps) what = "null taps";
     else if (n_frames < 1) what = "n_frames < 1";
-    else if (!(W >= 1 && W <= kbe_area::kMaxSide && H >= 1 && H <= kbe_area::kMaxSide)) what = "W or H outside 1..65535";
+    else if (!(W >= 1 && W <= kbe_rows::kMaxSide && H >= 1 && H <= kbe_rows::kMaxSide)) what = "W or H outside 1..65535";
     else if (stride_bytes < 3 * W) what = "stride_bytes < 3 W";
     else if (out_stride_bytes < 3 * W) what = "out_stride_bytes < 3 W";
     else if (!(radius >= 1 && radius <= ksh::kMaxRadius)) what = "radius outside 1..24";
@@ -170,7 +155,7 @@ KBE_SHARPEN_API int kbe_sharpen_u8(const uint8_t* const* frames_u8, int n_frames
     else if (!(threshold >= 0 && threshold <= ksh::kMaxThreshold)) what = "threshold outside 0..255";
     for (int i = 0; !what && i < n_frames; i++)
         if (!frames_u8[i] || !out_u8[i]) what = frames_u8[i] ? "null element of out_u8" : "null element of frames_u8";
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_sharpen_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_sharpen_u8", what);
 
     SharpenArgs a;
     for (int k = 0; k <= ksh::kMaxRadius; k++) a.taps.w[k] = k <= radius ? taps[k] : 0u;
@@ -183,11 +168,9 @@ KBE_SHARPEN_API int kbe_sharpen_u8(const uint8_t* const* frames_u8, int n_frames
     a.threshold = threshold;
     const dim3 tiles(blocks_for((size_t) W, kTileX), blocks_for((size_t) H, kTileY));
     for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) {
-            a.src[i] = i < nf ? frames_u8[f0 + i] : nullptr;
-            a.dst[i] = i < nf ? out_u8[f0 + i] : nullptr;
-        }
+        const int nf = launch_frames(n_frames, f0, kFramesPerLaunch);
+        fill_slots(a.src, frames_u8, f0, nf);
+        fill_slots(a.dst, out_u8, f0, nf);
         hipLaunchKernelGGL(k_sharpen, dim3(tiles.x, tiles.y, (unsigned) nf), dim3(kBlock), lds_bytes(radius), (hipStream_t) stream, a);
     }
     return launched("kbe_sharpen_u8");

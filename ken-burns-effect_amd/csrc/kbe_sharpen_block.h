@@ -39,7 +39,7 @@ KBE_AREA_HD bool taps_ok(const uint16_t* taps, int radius)
 
 KBE_AREA_HD bool shape_ok(int W, int H, int amount, int threshold)
 {
-    return W >= 1 && H >= 1 && W <= kbe_area::kMaxSide && H <= kbe_area::kMaxSide && amount >= 1 && amount <= kMaxAmount && threshold >= 0 && threshold <= kMaxThreshold;
+    return W >= 1 && H >= 1 && W <= kbe_rows::kMaxSide && H <= kbe_rows::kMaxSide && amount >= 1 && amount <= kMaxAmount && threshold >= 0 && threshold <= kMaxThreshold;
 }
 
 KBE_AREA_HD uint32_t clamped(int32_t i, uint32_t n)

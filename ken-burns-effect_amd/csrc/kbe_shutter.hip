@@ -1,6 +1,7 @@
 // kbe_shutter.hip -- kbe_shutter_mean_u8: every output frame the byte-wise mean of `samples` source frames that lie in HBM, for shutter.py
-// (include/kbe_shutter.h).  The arithmetic is kbe_shutter_block.h's add(), finish() and realign(), as they are; this file spreads the work
-// over the chip.  A streaming kernel: it reads S * 3 W H bytes and writes 3 W H per output, and nothing is read twice.
+// (include/kbe_shutter.h).  The arithmetic is kbe_shutter_block.h's add() and finish(), as they are, and the rows' bytes are taken and
+// stored by kbe_rows.h's realign() and store_piece(), which k_transition runs too; this file spreads the work over the chip.
+// A streaming kernel: it reads S * 3 W H bytes and writes 3 W H per output, and nothing is read twice.
 //
 // A row is a byte stream.  One lane makes one ALIGNED 16-byte piece of an output row; a wave takes kSpan = 1024 bytes of one row, counted from
 // the row's address rounded down to 16, and the four waves of a workgroup take four rows.  For every source the lane's 16 bytes start at the
@@ -9,7 +10,7 @@
 // dword, and only the dwords that hold a byte of the row: no address outside a row's dwords is touched -- and cuts its 16 bytes out with a
 // funnel shift by bytes.  No register is indexed by a variable.  Neighbouring lanes load each other's fifth dword: that costs L1 bandwidth,
 // not HBM traffic.  The sums are two 16-bit lanes per dword.  A piece that lies inside the row is stored as 16 bytes; the pieces at a row's
-// two ends as dwords and single bytes (the tail of kbe_area.hip); nothing outside a row's 3 W bytes is written.
+// two ends as dwords and single bytes (kbe_rows.h's store_piece, the tile kernels' too); nothing outside a row's 3 W bytes is written.
 //
 // The pointer tables travel as kernel arguments: a launch carries min(12, max(1, 96 / S)) output frames (the grid's z), so at most 96 source
 // pointers.  Every loop has a static bound (the S sources); no workgroup waits for another; no LDS, no scratch.
@@ -22,17 +23,14 @@ namespace ksh = kbe_shutter;
 
 namespace {
 
-constexpr int kOutputsPerLaunch = 12;                       // as the other filters' frames per launch
+constexpr int kOutputsPerLaunch = kbe_rows::kFramesPerLaunch;
 constexpr int kSourcesPerLaunch = 96;
 constexpr int kRows = 4;                                    // one wave per row
 constexpr int kLanes = 64;
 constexpr int kSpan = kLanes * ksh::kPiece;                 // 1024: the bytes of a row that one workgroup takes
 static_assert(kRows * kLanes == kBlock && kSpan == 1024 && kOutputsPerLaunch * 8 == kSourcesPerLaunch, "the kernel's layout");
 
-// four aligned dwords, loaded as one 16-byte piece at the alignment of a dword
-struct __attribute__((packed, aligned(4))) Dwords4 {
-    uint32_t x, y, z, w;
-};
+using kbe_rows::Dwords4;
 
 struct ShutterArgs {
     const uint8_t* src[kSourcesPerLaunch];                  // the sources of output i: src[i * S .. i * S + S - 1]
@@ -63,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void k_shutter_mean(const ShutterArgs a)
     const size_t row_at = (size_t) y * a.stride;
     // (inside the row, which is all but a row's first and last piece or two, every dword holds a byte of it.  One source at a time: taking
     // turns with it on the chip, four sources in flight per wave and the fifth dword fetched from the next lane's registers were both slower)
-    const bool inside = ksh::all_dwords_hold_a_byte(j0, row_bytes);
+    const bool inside = kbe_rows::all_dwords_hold_a_byte<ksh::kDwords>(j0, row_bytes);
     for (uint32_t s = 0; s < S; s++) {
         const uint8_t* const first = sources[s] + row_at + j0;                                // (before the row where j0 < 0: not read)
         const uint32_t b = (uint32_t) ((uintptr_t) first & 3u);
@@ -73,25 +71,14 @@ __global__ __launch_bounds__(kBlock) void k_shutter_mean(const ShutterArgs a)
             const Dwords4 four = *reinterpret_cast<const Dwords4*>(dwords);
             x[0] = four.x, x[1] = four.y, x[2] = four.z, x[3] = four.w, x[4] = dwords[4];
         } else {
-            for (int k = 0; k < 5; k++) x[k] = ksh::dword_holds_a_byte(j0, b, k, row_bytes) ? dwords[k] : 0u;
+            for (int k = 0; k < 5; k++) x[k] = kbe_rows::dword_holds_a_byte<ksh::kDwords>(j0, b, k, row_bytes) ? dwords[k] : 0u;
         }
         ksh::realign(x, b, w);
         ksh::add(acc, w);
     }
     uint32_t word[4];
     ksh::finish(acc, S, a.M, word);
-
-    uint8_t* const p = row - lead + at;                                                        // 16-byte aligned
-    const uint32_t lo = at < lead ? lead - at : 0u, hi = end - at < 16u ? end - at : 16u;
-    if (lo == 0u && hi == 16u) *reinterpret_cast<uint4*>(p) = make_uint4(word[0], word[1], word[2], word[3]);
-    else {
-        for (uint32_t d = 0; d < 4u; d++) {
-            if (lo <= 4u * d && 4u * d + 4u <= hi) reinterpret_cast<uint32_t*>(p)[d] = word[d];
-            else
-                for (uint32_t b = 4u * d; b < 4u * d + 4u; b++)
-                    if (lo <= b && b < hi) p[b] = (uint8_t) (word[d] >> (8u * (b & 3u)));
-        }
-    }
+    kbe_rows::store_piece(row, lead, end, at, word);
 }
 
 }  // namespace
@@ -121,24 +108,11 @@ KBE_SHUTTER_API int kbe_shutter_mean_u8(const uint8_t* const* frames_u8, int n_o
         if (!out_u8[i]) what = "null element of out_u8";
     // a lane reads its sources' bytes and writes the output's: an output may share no byte with a source of the call, nor with another output
     if (!what) {
-        const uintptr_t src_bytes = (uintptr_t) (H - 1) * (uintptr_t) stride_bytes + 3u * (uintptr_t) W;
-        const uintptr_t out_bytes = (uintptr_t) (H - 1) * (uintptr_t) out_stride_bytes + 3u * (uintptr_t) W;
-        for (int i = 0; !what && i < n_out; i++) {
-            const uintptr_t o0 = (uintptr_t) out_u8[i], o1 = o0 + out_bytes;
-            for (size_t j = 0; !what && j < n_sources; j++) {
-                const uintptr_t s0 = (uintptr_t) frames_u8[j];
-                if (o0 < s0 + src_bytes && s0 < o1) what = "an element of out_u8 overlaps a source frame";
-            }
-        }
-        for (int i = 0; !what && i < n_out; i++) {
-            const uintptr_t o0 = (uintptr_t) out_u8[i], o1 = o0 + out_bytes;
-            for (int j = i + 1; !what && j < n_out; j++) {
-                const uintptr_t q0 = (uintptr_t) out_u8[j];
-                if (o0 < q0 + out_bytes && q0 < o1) what = "an element of out_u8 overlaps another output";
-            }
-        }
+        const uintptr_t src_bytes = frame_extent(H, stride_bytes, 3u * (uintptr_t) W), out_bytes = frame_extent(H, out_stride_bytes, 3u * (uintptr_t) W);
+        if (any_overlap(out_u8, n_out, out_bytes, frames_u8, n_sources, src_bytes)) what = "an element of out_u8 overlaps a source frame";
+        else if (any_two_overlap(out_u8, n_out, out_bytes)) what = "an element of out_u8 overlaps another output";
     }
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_shutter_mean_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_shutter_mean_u8", what);
 
     ShutterArgs a;
     a.S = (uint32_t) samples;
@@ -151,9 +125,9 @@ KBE_SHUTTER_API int kbe_shutter_mean_u8(const uint8_t* const* frames_u8, int n_o
     // (a row's pieces begin up to 15 bytes before the row does)
     const dim3 spans(blocks_for((size_t) a.row_bytes + 15u, kSpan), blocks_for((size_t) H, kRows));
     for (int f0 = 0; f0 < n_out; f0 += per_launch) {
-        const int nf = n_out - f0 < per_launch ? n_out - f0 : per_launch;
-        for (int i = 0; i < kSourcesPerLaunch; i++) a.src[i] = i < nf * samples ? frames_u8[(size_t) f0 * samples + i] : nullptr;
-        for (int i = 0; i < kOutputsPerLaunch; i++) a.dst[i] = i < nf ? out_u8[f0 + i] : nullptr;
+        const int nf = launch_frames(n_out, f0, per_launch);
+        fill_slots(a.src, frames_u8, (size_t) f0 * samples, nf * samples);
+        fill_slots(a.dst, out_u8, f0, nf);
         hipLaunchKernelGGL(k_shutter_mean, dim3(spans.x, spans.y, (unsigned) nf), dim3(kBlock), 0, (hipStream_t) stream, a);
     }
     return launched("kbe_shutter_mean_u8");

@@ -1,6 +1,6 @@
 // kbe_transition.hip -- kbe_transition_u8: every output frame made of two source frames that lie in HBM -- a dissolve, a wipe with a soft edge, a
 // fade through a colour --, for transition.py (include/kbe_transition.h).  The arithmetic is kbe_transition_block.h's plan() and blend_piece()
-// and kbe_shutter_block.h's realign(), as they are; this file spreads the work over the chip.  A streaming kernel in the shape of
+// and kbe_rows.h's realign() and store_piece(), as they are; this file spreads the work over the chip.  A streaming kernel in the shape of
 // k_shutter_mean (kbe_shutter.hip): it reads up to 2 * 3 W H bytes and writes 3 W H per output, and nothing is read twice.
 //
 // A row is a byte stream.  One lane makes one ALIGNED 16-byte piece of an output row; a wave takes kSpan = 1024 bytes of one row, counted from
@@ -28,12 +28,9 @@ constexpr int kFramesPerLaunch = KBE_TRANSITION_FRAMES_PER_LAUNCH;
 constexpr int kRows = 4;                                    // one wave per row
 constexpr int kLanes = 64;
 constexpr int kSpan = kLanes * ktr::kPiece;                 // 1024: the bytes of a row that one workgroup takes
-static_assert(kRows * kLanes == kBlock && kSpan == 1024 && kFramesPerLaunch == 12, "the kernel's layout");
+static_assert(kRows * kLanes == kBlock && kSpan == 1024 && kFramesPerLaunch == kbe_rows::kFramesPerLaunch, "the kernel's layout");
 
-// four aligned dwords, loaded as one 16-byte piece at the alignment of a dword
-struct __attribute__((packed, aligned(4))) Dwords4 {
-    uint32_t x, y, z, w;
-};
+using kbe_rows::Dwords4;
 
 struct TransitionArgs {
     const uint8_t* from[kFramesPerLaunch];
@@ -54,7 +51,7 @@ __device__ __forceinline__ uint32_t load_dwords(const uint8_t* first, long j0, l
         const Dwords4 four = *reinterpret_cast<const Dwords4*>(dwords);
         x[0] = four.x, x[1] = four.y, x[2] = four.z, x[3] = four.w, x[4] = dwords[4];
     } else {
-        for (int k = 0; k < 5; k++) x[k] = ktr::dword_holds_a_byte(j0, b, k, row_bytes) ? dwords[k] : 0u;
+        for (int k = 0; k < 5; k++) x[k] = kbe_rows::dword_holds_a_byte<ktr::kDwords>(j0, b, k, row_bytes) ? dwords[k] : 0u;
     }
     return b;
 }
@@ -73,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void k_transition(const TransitionArgs a)
     f.p = a.progress[blockIdx.z];
     const ktr::Plan q = ktr::plan(f, j0, y);
     const size_t row_at = (size_t) y * a.stride;
-    const bool inside = ktr::all_dwords_hold_a_byte(j0, row_bytes);
+    const bool inside = kbe_rows::all_dwords_hold_a_byte<ktr::kDwords>(j0, row_bytes);
     uint32_t xf[5] = {0u, 0u, 0u, 0u, 0u}, xt[5] = {0u, 0u, 0u, 0u, 0u}, bf = 0u, bt = 0u, from[4], to[4], word[4];
     // (before the row where j0 < 0: not read)
     if (q.from) bf = load_dwords(a.from[blockIdx.z] + row_at + j0, j0, row_bytes, inside, xf);
@@ -81,18 +78,7 @@ __global__ __launch_bounds__(kBlock) void k_transition(const TransitionArgs a)
     ktr::realign(xf, bf, from);
     ktr::realign(xt, bt, to);
     ktr::blend_piece(f, q, from, to, word);
-
-    uint8_t* const p = row - lead + at;                                                        // 16-byte aligned
-    const uint32_t lo = at < lead ? lead - at : 0u, hi = end - at < 16u ? end - at : 16u;
-    if (lo == 0u && hi == 16u) *reinterpret_cast<uint4*>(p) = make_uint4(word[0], word[1], word[2], word[3]);
-    else {
-        for (uint32_t d = 0; d < 4u; d++) {
-            if (lo <= 4u * d && 4u * d + 4u <= hi) reinterpret_cast<uint32_t*>(p)[d] = word[d];
-            else
-                for (uint32_t b = 4u * d; b < 4u * d + 4u; b++)
-                    if (lo <= b && b < hi) p[b] = (uint8_t) (word[d] >> (8u * (b & 3u)));
-        }
-    }
+    kbe_rows::store_piece(row, lead, end, at, word);
 }
 
 }  // namespace
@@ -128,24 +114,11 @@ KBE_TRANSITION_API int kbe_transition_u8(const uint8_t* const* from_u8, const ui
     }
     // a lane reads its sources' bytes and writes the output's: an output may share no byte with a source of the call, nor with another output
     if (!what) {
-        const uintptr_t src_bytes = (uintptr_t) (H - 1) * (uintptr_t) stride_bytes + 3u * (uintptr_t) W;
-        const uintptr_t out_bytes = (uintptr_t) (H - 1) * (uintptr_t) out_stride_bytes + 3u * (uintptr_t) W;
-        for (int i = 0; !what && i < n; i++) {
-            const uintptr_t o0 = (uintptr_t) out_u8[i], o1 = o0 + out_bytes;
-            for (int j = 0; !what && j < n; j++) {
-                const uintptr_t s0 = (uintptr_t) from_u8[j], t0 = (uintptr_t) to_u8[j];
-                if ((o0 < s0 + src_bytes && s0 < o1) || (o0 < t0 + src_bytes && t0 < o1)) what = "an element of out_u8 overlaps a source frame";
-            }
-        }
-        for (int i = 0; !what && i < n; i++) {
-            const uintptr_t o0 = (uintptr_t) out_u8[i], o1 = o0 + out_bytes;
-            for (int j = i + 1; !what && j < n; j++) {
-                const uintptr_t q0 = (uintptr_t) out_u8[j];
-                if (o0 < q0 + out_bytes && q0 < o1) what = "an element of out_u8 overlaps another output";
-            }
-        }
+        const uintptr_t src_bytes = frame_extent(H, stride_bytes, 3u * (uintptr_t) W), out_bytes = frame_extent(H, out_stride_bytes, 3u * (uintptr_t) W);
+        if (any_overlap(out_u8, n, out_bytes, from_u8, n, src_bytes) || any_overlap(out_u8, n, out_bytes, to_u8, n, src_bytes)) what = "an element of out_u8 overlaps a source frame";
+        else if (any_two_overlap(out_u8, n, out_bytes)) what = "an element of out_u8 overlaps another output";
     }
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_transition_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_transition_u8", what);
 
     TransitionArgs a;
     a.frame.kind = (uint32_t) kind;
@@ -161,13 +134,11 @@ KBE_TRANSITION_API int kbe_transition_u8(const uint8_t* const* from_u8, const ui
     // (a row's pieces begin up to 15 bytes before the row does)
     const dim3 spans(blocks_for((size_t) a.row_bytes + 15u, kSpan), blocks_for((size_t) H, kRows));
     for (int f0 = 0; f0 < n; f0 += kFramesPerLaunch) {
-        const int nf = n - f0 < kFramesPerLaunch ? n - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) {
-            a.from[i] = i < nf ? from_u8[f0 + i] : nullptr;
-            a.to[i] = i < nf ? to_u8[f0 + i] : nullptr;
-            a.dst[i] = i < nf ? out_u8[f0 + i] : nullptr;
-            a.progress[i] = i < nf ? (uint32_t) progress[f0 + i] : 0u;
-        }
+        const int nf = launch_frames(n, f0, kFramesPerLaunch);
+        fill_slots(a.from, from_u8, f0, nf);
+        fill_slots(a.to, to_u8, f0, nf);
+        fill_slots(a.dst, out_u8, f0, nf);
+        for (int i = 0; i < kFramesPerLaunch; i++) a.progress[i] = i < nf ? (uint32_t) progress[f0 + i] : 0u;
         hipLaunchKernelGGL(k_transition, dim3(spans.x, spans.y, (unsigned) nf), dim3(kBlock), 0, (hipStream_t) stream, a);
     }
     return launched("kbe_transition_u8");

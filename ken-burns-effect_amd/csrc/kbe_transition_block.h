@@ -23,7 +23,7 @@
 //     i / 3 + 1 -- and (r + i) 11 >> 5 for the last byte's, r + i <= 17.  A lane in the soft edge takes six weights, not sixteen.
 //   * a piece whose weights are all 0 or all 256 is a copy of one source: plan() says which sources a piece reads, and the kernel loads no other.
 //     The weights of a wipe are monotone along its axis: the first and the last byte's decide.  The fade reads one source.
-//   * a piece of a source starts anywhere: kbe_shutter_block.h's realign cuts it out of the five aligned dwords that hold it.
+//   * a piece of a source starts anywhere: kbe_rows.h's realign cuts it out of the five aligned dwords that hold it.
 #pragma once
 #include "kbe_shutter_block.h"
 
@@ -31,13 +31,12 @@
 
 namespace kbe_transition {
 
-using kbe_shutter::all_dwords_hold_a_byte;
-using kbe_shutter::dword_holds_a_byte;
-using kbe_shutter::realign;
+using kbe_rows::kMaxSide;
+using kbe_rows::kPiece;                       // bytes: what one lane of the kernel loads from a source, and stores
+using kbe_rows::realign;
+using kbe_shutter::kDwords;
 
-constexpr int kMaxSide = 65535;
 constexpr int kMaxSoftness = 65535;
-constexpr int kPiece = 16;                    // bytes: what one lane of the kernel loads from a source, and stores
 constexpr int kKinds = 6;
 enum Kind : uint32_t { kDissolve = 0, kWipeRight = 1, kWipeLeft = 2, kWipeDown = 3, kWipeUp = 4, kFade = 5 };
 
@@ -167,38 +166,30 @@ KBE_TRANSITION_HD void blend_piece(const Frame& f, const Plan& q, const uint32_t
 #if !defined(__HIPCC__)
 // One output row on a CPU, serially, the way the kernel takes it: pieces of 16 bytes at the OUTPUT row's alignment (`lead` = its address
 // modulo 16, given by the caller so that a test can walk through all sixteen), each source realigned by its own address modulo 4
-// (from_class, to_class: the address of the source row's first byte, any number congruent to it modulo 4).  The aligned dwords are put
-// together byte by byte from the row alone -- 0 where the row has no byte or the dword is not loaded --, so nothing outside a row is read;
-// a source that the plan does not read is not looked at: its dwords are 0xDD.
-inline void source_piece(const uint8_t* row, uint32_t row_class, bool read, long j0, long row_bytes, uint32_t w[4])
+// (from_class, to_class: the address of the source row's first byte, any number congruent to it modulo 4).  The walk over the pieces, the
+// aligned dwords of a row and the store of a piece are kbe_rows.h's: nothing outside a row is read or written; a source that the plan does
+// not read is not looked at: its dwords are 0xDD.
+inline void source_piece(const uint8_t* row, uint32_t row_class, bool read, long j0, long row_bytes, uint32_t (&w)[kDwords])
 {
     const uint32_t b = (uint32_t) (((long) row_class + j0) & 3);
-    uint8_t bytes[20];
-    for (long i = 0; i < 20; i++) {
-        const long j = j0 - (long) b + i;
-        const bool loaded = all_dwords_hold_a_byte(j0, row_bytes) || dword_holds_a_byte(j0, b, (int) (i / 4), row_bytes);
-        bytes[i] = !read ? (uint8_t) 0xDD : loaded && j >= 0 && j < row_bytes ? row[j] : (uint8_t) 0;
-    }
-    uint32_t x[5];
-    memcpy(x, bytes, 20);
+    uint32_t x[kDwords + 1];
+    if (read) kbe_rows::aligned_dwords<kDwords>(row, j0, b, row_bytes, x);
+    else memset(x, 0xDD, sizeof(x));
     realign(x, b, w);
 }
 
 inline void blend_row(const Frame& f, const uint8_t* from, const uint8_t* to, uint32_t from_class, uint32_t to_class, uint32_t y, uint32_t lead, uint8_t* out)
 {
     const long row_bytes = 3l * (long) f.W;
-    for (long at = 0; at < (long) lead + row_bytes; at += kPiece) {
-        const long j0 = at - (long) lead;
+    kbe_rows::for_each_piece(row_bytes, lead, [&](uint32_t at) {
+        const long j0 = (long) at - (long) lead;
         const Plan q = plan(f, j0, y);
         uint32_t a[4], b[4], word[4];
-        uint8_t piece[16];
         source_piece(from, from_class, q.from, j0, row_bytes, a);
         source_piece(to, to_class, q.to, j0, row_bytes, b);
         blend_piece(f, q, a, b, word);
-        memcpy(piece, word, 16);
-        for (long i = 0; i < kPiece; i++)
-            if (j0 + i >= 0 && j0 + i < row_bytes) out[j0 + i] = piece[i];
-    }
+        kbe_rows::store_piece(out, lead, lead + (uint32_t) row_bytes, at, word);
+    });
 }
 #endif
 

@@ -30,12 +30,9 @@ namespace {
 constexpr int kFramesPerLaunch = KBE_YUV_FRAMES_PER_LAUNCH;
 constexpr int kRowPairs = 4;                                // one wave per row pair
 constexpr int kLanes = 64;
-static_assert(kRowPairs * kLanes == kBlock && kFramesPerLaunch == 12 && ky::kFlagBGR == KBE_YUV_BGR, "the kernel's layout");
+static_assert(kRowPairs * kLanes == kBlock && kFramesPerLaunch == kbe_rows::kFramesPerLaunch && ky::kFlagBGR == KBE_YUV_BGR, "the kernel's layout");
 
-// four aligned dwords, loaded as one 16-byte piece at the alignment of a dword
-struct __attribute__((packed, aligned(4))) Dwords4 {
-    uint32_t x, y, z, w;
-};
+using kbe_rows::Dwords4;
 
 struct YuvArgs {
     const uint8_t* src[kFramesPerLaunch];
@@ -62,7 +59,7 @@ __device__ __forceinline__ void load_at_an_end(const uint8_t* first, uint32_t b,
 {
     const uint32_t* const dwords = reinterpret_cast<const uint32_t*>(first - b);
 #pragma unroll
-    for (int k = 0; k <= ky::kRunDwords; k++) x[k] = ky::dword_holds_a_byte(j0, b, k, row_bytes) ? dwords[k] : 0u;
+    for (int k = 0; k <= ky::kRunDwords; k++) x[k] = kbe_rows::dword_holds_a_byte<ky::kRunDwords>(j0, b, k, row_bytes) ? dwords[k] : 0u;
 }
 
 // the value of the lane to the left; the first lane's is `carry`
@@ -98,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void k_yuv420(const YuvArgs a)
         const uint8_t* const first_bot = first_top + (two ? a.stride : 0u);
         const uint32_t b_top = (uint32_t) ((uintptr_t) first_top & 3u), b_bot = (uint32_t) ((uintptr_t) first_bot & 3u);
         uint32_t xt[ky::kRunDwords + 1], xb[ky::kRunDwords + 1];
-        if (live && ky::all_dwords_hold_a_byte(j0, row_bytes)) {
+        if (live && kbe_rows::all_dwords_hold_a_byte<ky::kRunDwords>(j0, row_bytes)) {
             load_inside(first_top, b_top, xt);
             if (two) load_inside(first_bot, b_bot, xb);
         } else if (live) {
@@ -155,23 +152,11 @@ KBE_YUV_API int kbe_yuv420_u8(const uint8_t* const* frames_u8, int n_frames, int
         if (!out_u8[i]) what = "null element of out_u8";
     // a lane reads its frame's bytes and writes the payload's: a payload may share no byte with a source of the call, nor with another payload
     if (!what) {
-        const uintptr_t src_bytes = (uintptr_t) (H - 1) * (uintptr_t) stride_bytes + 3u * (uintptr_t) W, out_bytes = (uintptr_t) ky::payload_bytes(W, H);
-        for (int i = 0; !what && i < n_frames; i++) {
-            const uintptr_t o0 = (uintptr_t) out_u8[i], o1 = o0 + out_bytes;
-            for (int j = 0; !what && j < n_frames; j++) {
-                const uintptr_t s0 = (uintptr_t) frames_u8[j];
-                if (o0 < s0 + src_bytes && s0 < o1) what = "an element of out_u8 overlaps a source frame";
-            }
-        }
-        for (int i = 0; !what && i < n_frames; i++) {
-            const uintptr_t o0 = (uintptr_t) out_u8[i], o1 = o0 + out_bytes;
-            for (int j = i + 1; !what && j < n_frames; j++) {
-                const uintptr_t q0 = (uintptr_t) out_u8[j];
-                if (o0 < q0 + out_bytes && q0 < o1) what = "an element of out_u8 overlaps another output";
-            }
-        }
+        const uintptr_t src_bytes = frame_extent(H, stride_bytes, 3u * (uintptr_t) W), out_bytes = (uintptr_t) ky::payload_bytes(W, H);
+        if (any_overlap(out_u8, n_frames, out_bytes, frames_u8, n_frames, src_bytes)) what = "an element of out_u8 overlaps a source frame";
+        else if (any_two_overlap(out_u8, n_frames, out_bytes)) what = "an element of out_u8 overlaps another output";
     }
-    if (what) { snprintf(g_err, sizeof(g_err), "kbe_yuv420_u8: %s", what); return KBE_E_INVALID; }
+    if (what) return refuse("kbe_yuv420_u8", what);
 
     YuvArgs a;
     a.k = ky::coef(flags);
@@ -180,8 +165,9 @@ KBE_YUV_API int kbe_yuv420_u8(const uint8_t* const* frames_u8, int n_frames, int
     a.stride = (uint32_t) stride_bytes;
     const unsigned pairs = blocks_for((size_t) ((H + 1) / 2), kRowPairs);
     for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
-        const int nf = n_frames - f0 < kFramesPerLaunch ? n_frames - f0 : kFramesPerLaunch;
-        for (int i = 0; i < kFramesPerLaunch; i++) a.src[i] = i < nf ? frames_u8[f0 + i] : nullptr, a.dst[i] = i < nf ? out_u8[f0 + i] : nullptr;
+        const int nf = launch_frames(n_frames, f0, kFramesPerLaunch);
+        fill_slots(a.src, frames_u8, f0, nf);
+        fill_slots(a.dst, out_u8, f0, nf);
         hipLaunchKernelGGL(k_yuv420, dim3(pairs, 1, (unsigned) nf), dim3(kBlock), 0, (hipStream_t) stream, a);
     }
     return launched("kbe_yuv420_u8");

@@ -24,7 +24,7 @@
 //     twice.  Doubling the sums and n leaves floor((sum + 128 n) / (256 n)) what it was, so n = 2 and n = 1 are the n = 4 form on repeated
 //     pixels: cell = (17344 + the four dots) >> 10, 17344 = 512 + 128 * 1024 - 4 * 255 * 112, at most 245824 >> 10 = 240.
 //   * a lane takes a RUN of kRun = 16 pixels, 8 cells, of a row pair: 48 source bytes of each row, which start anywhere; they are cut out of
-//     the 13 ALIGNED dwords that hold them (realign, as csrc/kbe_shutter_block.h does it), and pixel i is cut out of those (pixel).
+//     the 13 ALIGNED dwords that hold them (csrc/kbe_rows.h's realign), and pixel i is cut out of those (pixel).
 //   * the four output streams of a row pair -- the two Y rows, the Cb row, the Cr row -- start anywhere too, each at an alignment of its
 //     own.  A lane's bytes of a stream are moved up by m = the stream's address modulo 4 with the previous lane's last dword (shift_in), so
 //     that every lane stores ALIGNED dwords (store_piece); byte stores are left to a stream's two ends.
@@ -39,9 +39,14 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "kbe_rows.h"
+
 namespace kbe_yuv {
 
-constexpr int kMaxSide = 65535;
+using kbe_rows::align_bytes;
+using kbe_rows::kMaxSide;
+using kbe_rows::realign;
+
 constexpr int kFlagBGR = 1;                   // KBE_YUV_BGR
 constexpr int kRun = 16;                      // pixels of a row that one lane of the kernel takes: 8 cells
 constexpr int kRunDwords = 12;                // ... 48 source bytes of each of its two rows
@@ -107,16 +112,6 @@ KBE_YUV_HD uint32_t dot4(uint32_t a, uint32_t w, uint32_t c)
 #endif
 }
 
-// the dword that starts b bytes into lo, continued in hi (little endian), 0 <= b <= 3: the chip's byte-align
-KBE_YUV_HD uint32_t align_bytes(uint32_t hi, uint32_t lo, uint32_t b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbyte(hi, lo, b);
-#else
-    return (uint32_t) ((((uint64_t) hi << 32) | (uint64_t) lo) >> (8u * b));
-#endif
-}
-
 // byte 1 of a, b, c and d as the bytes 0, 1, 2 and 3 of one dword: on the device three byte permutes
 KBE_YUV_HD uint32_t bytes1(uint32_t a, uint32_t b, uint32_t c, uint32_t d)
 {
@@ -138,16 +133,6 @@ KBE_YUV_HD uint32_t luma_word(uint32_t p, uint32_t wy)
 KBE_YUV_HD uint32_t chroma_of(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t w, uint32_t x)
 {
     return dot4(p3 ^ x, w, dot4(p2 ^ x, w, dot4(p1 ^ x, w, dot4(p0 ^ x, w, kChromaAddend)))) >> 10;
-}
-
-// the n dwords that start b bytes into the n + 1 dwords x: a funnel shift by bytes.  With b = 0 nothing of x[n] is read
-template <int N>
-KBE_YUV_HD void realign(const uint32_t (&x)[N + 1], uint32_t b, uint32_t (&w)[N])
-{
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int k = 0; k < N; k++) w[k] = align_bytes(x[k + 1], x[k], b);
 }
 
 // pixel i of a run, as a dword, from the run's 12 dwords; byte 3 of the last pixel's is 0.  i is a constant wherever this is called
@@ -192,20 +177,8 @@ KBE_YUV_HD void run(const uint32_t (&top)[kRunDwords], const uint32_t (&bot)[kRu
     }
 }
 
-// Which of the 13 ALIGNED dwords around a run's 48 source bytes hold a byte of the row.  The row's bytes are j in [0, row_bytes); the run's are
-// j0 .. j0 + 47 and begin b bytes into dword 0; dword k covers j0 - b + 4 k .. j0 - b + 4 k + 3.  A dword that holds no byte of the row is not
-// loaded: its address may not exist.  Nothing is taken from dword 12 where b = 0.
-KBE_YUV_HD bool dword_holds_a_byte(int j0, uint32_t b, int k, int row_bytes)
-{
-    const int first = j0 - (int) b + 4 * k;
-    return first + 3 >= 0 && first < row_bytes && (k < kRunDwords || b != 0u);
-}
-
-// ... and whether all 13 do, whatever b is: then a lane loads them as three 16-byte pieces at dword alignment and one dword
-KBE_YUV_HD bool all_dwords_hold_a_byte(int j0, int row_bytes)
-{
-    return j0 >= 0 && j0 + 4 * kRunDwords < row_bytes;
-}
+// (Which of the 13 ALIGNED dwords around a run's 48 source bytes hold a byte of the row, and so may be loaded: kbe_rows.h's
+// dword_holds_a_byte<kRunDwords> and all_dwords_hold_a_byte<kRunDwords>, on the kernel's int.)
 
 // A lane's N dwords of an output stream, moved up by m = the stream's address modulo 4 -> N + 1 dwords, out[0] beginning with the last m
 // bytes of the previous lane's last dword `prev`; out[N] holds the lane's own last m bytes, which the stream's last lane stores itself
@@ -309,8 +282,8 @@ KBE_YUV_HD void store_run(const Streams& s, int g, int W, int cw, const uint32_t
 #if !defined(__HIPCC__)
 // One frame on a CPU, serially, the way the kernel takes it: row pair by row pair, lane by lane.  The alignments are GIVEN, so that a test can
 // walk through all of them: src_class = the address of the source's first byte, out_class = that of the payload's first byte (any numbers
-// congruent to them modulo 16).  The aligned source dwords are put together byte by byte from the row alone -- 0 where the row has no byte
-// or the dword is not loaded --, so nothing outside a row is read; the payload is written through store_piece alone.
+// congruent to them modulo 16).  The aligned source dwords are kbe_rows.h's aligned_dwords -- 0 where the row has no byte or the dword is
+// not loaded --, so nothing outside a row is read; the payload is written through store_piece alone.
 inline void convert_frame(const uint8_t* src, long stride, long W, long H, int flags, uint32_t src_class, uint32_t out_class, uint8_t* out)
 {
     const Coef k = coef(flags);
@@ -328,16 +301,9 @@ inline void convert_frame(const uint8_t* src, long stride, long W, long H, int f
             uint32_t rows[2][kRunDwords];
             for (int r = 0; r < 2; r++) {
                 const long y = 2 * cy + (two ? r : 0);
-                const uint8_t* row = src + y * stride;
                 const uint32_t b = (uint32_t) (((long) src_class + y * stride + j0) & 3);
-                uint8_t bytes[4 * (kRunDwords + 1)];
-                for (long i = 0; i < 4 * (kRunDwords + 1); i++) {
-                    const long j = j0 - (long) b + i;
-                    const bool loaded = all_dwords_hold_a_byte((int) j0, (int) row_bytes) || dword_holds_a_byte((int) j0, b, (int) (i / 4), (int) row_bytes);
-                    bytes[i] = loaded && j >= 0 && j < row_bytes ? row[j] : (uint8_t) 0;
-                }
                 uint32_t x[kRunDwords + 1];
-                memcpy(x, bytes, sizeof(x));
+                kbe_rows::aligned_dwords<kRunDwords>(src + y * stride, j0, b, row_bytes, x);
                 realign<kRunDwords>(x, b, rows[r]);
             }
             const long x0 = kRun * g;

@@ -1,6 +1,10 @@
 """What tests/test_filter_sweeps_gpu.py rests on, without a GPU (tests/filter_sweep_cases.py): the sweeps' parameters reach every alignment class
-of the three kernels' tile store and row fetch, by the launch arithmetic alone; the exact area reduction by prefix sums equals the headers and
-the twins wherever both exist, the sides' limit among them; and every frame that makes a radius visible is sensitive to it."""
+of the tile store and row fetch that the kernels share (csrc/kbe_rows.h), by the launch arithmetic alone; that header itself, executed
+serially (tests/rows_check.cpp); the exact area reduction by prefix sums equals the headers and the twins wherever both exist, the sides'
+limit among them; and every frame that makes a radius visible is sensitive to it."""
+import re
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -8,6 +12,37 @@ import area_cases as ac
 import crop_area_cases as cc
 import dof_cases as dc
 import filter_sweep_cases as fc
+import twins
+
+
+# -- the shared row fetch and piece store, as compiled ---------------------------------------------
+def test_the_rows_header_is_the_bytes_themselves():
+    """rows_check.cpp builds.  store_piece over rows of 1..80 bytes at every lead, into 0x5A between bands: every byte of the row written
+    exactly once, nothing else changed, and every piece on the path the rule says -- counted here again from the rule: a piece whose 16
+    bytes are all the row's goes as 16 bytes; of any other, a dword whose four bytes are all the row's as a dword, the rest as bytes.  The
+    tile row at real addresses, the fetch arithmetic, realign<4, 6, 12> and the dwords' rule by brute force: no mismatch."""
+    out = subprocess.run([twins.built('rows_check'), 'brute'], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, (out.stdout + out.stderr)[-1000:]
+    m = re.search(r'brute: pieces (\d+), piece mismatches (\d+), whole pieces (\d+), dwords (\d+), bytes (\d+), tile rows (\d+), tile row mismatches (\d+), fetches (\d+), '
+                  r'fetch mismatches (\d+), realign mismatches (\d+), dwords asked (\d+), dword rule mismatches (\d+)', out.stdout)
+    pieces, piece_bad, whole, dwords, single, tile_rows, tile_bad, fetches, fetch_bad, realign_bad, asked, rule_bad = (int(v) for v in m.groups())
+    want = {'pieces': 0, 'whole': 0, 'dwords': 0, 'bytes': 0}
+    for n in range(1, 81):
+        for lead in range(16):
+            for at in range(0, lead + n, 16):
+                mine = [lead <= at + i < lead + n for i in range(16)]
+                want['pieces'] += 1
+                if all(mine):
+                    want['whole'] += 1
+                    continue
+                for d in range(4):
+                    four = mine[4 * d:4 * d + 4]
+                    want['dwords' if all(four) else 'bytes'] += 1 if all(four) else sum(four)
+    assert want['whole'] > 0 and want['dwords'] > 0 and want['bytes'] > 0
+    assert (pieces, whole, dwords, single) == (want['pieces'], want['whole'], want['dwords'], want['bytes'])
+    assert (tile_rows, fetches) == (64 * 16, 40 * 4)
+    assert asked == sum((n + 3 + 19 + 1) * 4 * (N + 1) for N in (4, 12) for n in range(1, 41))
+    assert (piece_bad, tile_bad, fetch_bad, realign_bad, rule_bad) == (0, 0, 0, 0, 0)
 
 
 # -- the classes -----------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """The three byte-frame filters on the GPU (kbe_area_reduce_u8, kbe_crop_area_u8, kbe_dof_u8) where their own test modules do not reach: every
-alignment class of the tile store and of the row fetch, which each kernel has a copy of; the sides' limit of 65535; and the radius of the blur
+alignment class of the tile store and of the row fetch -- one definition, csrc/kbe_rows.h, which every tile kernel runs at its own loop shape (so
+the sweeps over these three also hold kbe_enlarge_u8's and kbe_sharpen_u8's store) --; the sides' limit of 65535; and the radius of the blur
 as the device computes it, at its ties, at products that overflow and on subnormal depths.  Byte for byte against the twins, or at the sides'
 limit against references that work there (tests/filter_sweep_cases.py; what they rest on: tests/test_filter_sweeps.py), every buffer from
 guarded.Guard on both poisons."""
