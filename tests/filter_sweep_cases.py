@@ -1,12 +1,17 @@
-"""What tests/test_filter_sweeps.py (CPU) and tests/test_filter_sweeps_gpu.py share: the parameters of the sweeps over the three byte-frame
-filters (kbe_area_reduce_u8, kbe_crop_area_u8, kbe_dof_u8), the alignment classes those parameters reach -- computed from the kernels' launch
-arithmetic alone --, an exact area reduction that needs no weight matrix, for the sides' limit, and the frames that make a radius visible.
+"""What tests/test_filter_sweeps.py (CPU) and tests/test_filter_sweeps_gpu.py share: the parameters of the sweeps over the five tile
+filters (kbe_area_reduce_u8, kbe_crop_area_u8, kbe_dof_u8, kbe_enlarge_u8, kbe_sharpen_u8), the alignment classes those parameters reach --
+computed from the kernels' launch arithmetic alone --, an exact area reduction that needs no weight matrix, for the sides' limit, and the
+frames that make a radius visible.
 
-The code the sweeps are about is not in the *_block.h headers and exists once per kernel (csrc/kbe_area.hip, kbe_crop_area.hip, kbe_dof.hip):
+The code the sweeps are about is not in the *_block.h headers and exists once per kernel (csrc/kbe_area.hip, kbe_crop_area.hip, kbe_dof.hip,
+kbe_enlarge.hip, kbe_sharpen.hip):
   the tile store    a tile's row of nx <= 64 pixels is put together in LDS `lead` = (its address mod 16) bytes into an LDS row and written as
                     16-byte pieces, dwords and single bytes: its class is (lead, nx), 16 x 64 of them;
   the row fetch     a staged row of `len` pixels is fetched as the aligned dwords from `shift` = (its address & 3) bytes before it,
-                    (shift + 3 len + 3) >> 2 of them: its class is (shift, 3 len mod 4), 4 x 4 of them."""
+                    (shift + 3 len + 3) >> 2 of them: its class is (shift, 3 len mod 4), 4 x 4 of them;
+  sharpen's halo    a staged row lies behind a left halo of `left` pixels that the frame does not have, rounded up to a dword, and `shift`
+                    bytes on; `right` pixels are repeated behind it.  left is 0 or R: its class is (shift, R, which borders, right);
+  enlarge's LDS row a raw row of up to 68 pixels at a shift of up to 3 fills the 52 dwords an LDS row has, and up to 20 rows are staged."""
 import functools
 
 import numpy as np
@@ -14,20 +19,25 @@ import numpy as np
 import area_cases as ac
 import crop_area_cases as cc
 import dof_cases as dc
+import enlarge_cases as ec
 import gif_cases as gc
+import sharpen_cases as sc
 
 # -- the kernels' layout, as far as the classes depend on it -------------------------------------
 TILE_X = 64
-TILE_Y = {'area': 4, 'crop_area': 4, 'dof': 16}                    # kTileY
+TILE_Y = {'area': 4, 'crop_area': 4, 'dof': 16, 'enlarge': 16, 'sharpen': 32}        # kTileY
 STRIP_ROWS, STRIP_PX = 16, {'area': 340, 'crop_area': 339}         # kStripRows, kStripPx: a strip of the source (of the patch)
 ALLOCATION = 512                                                   # every allocation starts on a multiple of it (tests/guarded.py); the GPU tests assert it
+
+RAW_PX, RAW_ROWS = TILE_X + 4, TILE_Y['enlarge'] + 4               # enlarge's kRawPx, kRawRows: the taps of 64 (16) targets and the second taps
+MAX_RADIUS = 24                                                    # sharpen's kMaxRadius
 
 EVERY_STORE_CLASS = frozenset((lead, nx) for lead in range(16) for nx in range(1, TILE_X + 1))
 EVERY_FETCH_CLASS = frozenset((shift, rest) for shift in range(4) for rest in range(4))
 
 
 def store_classes(w, h, out_stride, shift=0):
-    """{(lead, nx)} of an output of w x h pixels, its rows out_stride bytes apart, `shift` bytes off its allocation: the same for the three
+    """{(lead, nx)} of an output of w x h pixels, its rows out_stride bytes apart, `shift` bytes off its allocation: the same for the five
     kernels -- a tile is 64 pixels across in all of them, and a tile's row starts 192 bytes after its left neighbour's."""
     assert ALLOCATION % 16 == 0
     return {((shift + oy * out_stride + 3 * ox0) % 16, min(TILE_X, w - ox0)) for oy in range(h) for ox0 in range(0, w, TILE_X)}
@@ -82,6 +92,77 @@ def dof_fetch_classes(W, H, R, stride, src_shift):
     return found
 
 
+def _sharpen_tiles(W, R):
+    """(fx, lx, left, right) of k_sharpen's tiles across: the frame's pixels [fx, lx) are staged, `left` and `right` pixels of the tile's halo
+    of R lie beyond the frame."""
+    for x0 in range(0, W, TILE_X):
+        nx = min(TILE_X, W - x0)
+        fx, lx = max(x0 - R, 0), min(x0 + nx + R, W)
+        yield fx, lx, fx + R - x0, x0 + nx + R - lx
+
+
+def _sharpen_rows(H, R):
+    """The frame rows of k_sharpen's staged rows, tile row by tile row: staged row r of the tile at y0 is frame row clamp(y0 - R + r)."""
+    for y0 in range(0, H, TILE_Y['sharpen']):
+        ny = min(TILE_Y['sharpen'], H - y0)
+        yield [min(max(y0 - R + r, 0), H - 1) for r in range(ny + 2 * R)]
+
+
+def sharpen_fetch_classes(W, H, R, stride, src_shift):
+    """{(shift, 3 span mod 4)} of k_sharpen: per tile its pixels and up to R more on either side, as far as the frame goes, of every staged row
+    -- the rows beyond the frame are the border rows again."""
+    found = set()
+    for fx, lx, _, _ in _sharpen_tiles(W, R):
+        for rows in _sharpen_rows(H, R):
+            found |= {_row_class(src_shift + fy * stride + 3 * fx, lx - fx) for fy in rows}
+    return found
+
+
+def sharpen_stage_classes(W, H, R, stride, src_shift):
+    """{(shift, R, border)} of k_sharpen's staged rows; border: 'neither', 'left', ('right', right) or ('both', right) -- which of the
+    tile's halos lie beyond the frame, and by how many pixels the right one does.  (The left one does by R or not at all: a tile starts at a
+    multiple of 64 > R.)"""
+    found = set()
+    for fx, lx, left, right in _sharpen_tiles(W, R):
+        assert left in (0, R) and 0 <= right <= R
+        border = (('both', right) if right else 'left') if left else (('right', right) if right else 'neither')
+        for rows in _sharpen_rows(H, R):
+            found |= {((src_shift + fy * stride + 3 * fx) % 4, R, border) for fy in rows}
+    return found
+
+
+def _enlarge_spans(n_in, n_out, tile):
+    """[p0, p1) of the patch under each tile of `tile` targets of an axis: the first tap of its first target to the last tap of its last, both
+    clamped (enlarge_cases.axis)."""
+    taps = ec.axis(n_in, n_out)[1]
+    return [(int(taps[o0, 0]), int(taps[min(o0 + tile, n_out) - 1, 3]) + 1) for o0 in range(0, n_out, tile)]
+
+
+def enlarge_cuts(n_in, n_out, tile):
+    """[(whether the clamp at the patch's first pixel cuts the tile's span, whether the one at its last pixel does)] per tile of an axis, from
+    the positions themselves: i = floor(((2 x + 1) n_in - n_out) / (2 n_out)), the taps i - 1 .. i + 2."""
+    at = lambda x: ((2 * x + 1) * n_in - n_out) // (2 * n_out)                     # noqa: E731
+    return [(at(o0) - 1 < 0, at(min(o0 + tile, n_out) - 1) + 2 > n_in - 1) for o0 in range(0, n_out, tile)]
+
+
+def enlarge_fetch_classes(W, H, crop, size, stride, src_shift):
+    """({(shift, 3 len mod 4)}, the largest (len, shift), the most rows a tile stages) of k_enlarge: under a tile's span of the patch its raw
+    rectangle, one pixel and one row more where the crop starts on a half pixel, as far as the frame goes."""
+    (cw, ch), (w, h) = crop, size
+    (ipx, hx), (ipy, hy) = cc.start(W, cw), cc.start(H, ch)
+    found, longest, most = set(), (0, 0), 0
+    for px0, px1 in _enlarge_spans(cw, w, TILE_X):
+        for py0, py1 in _enlarge_spans(ch, h, TILE_Y['enlarge']):
+            rx0, rx1 = ipx + px0, min(ipx + px1 + hx, W)
+            ry0, ry1 = ipy + py0, min(ipy + py1 + hy, H)
+            for ry in range(ry0, ry1):
+                at = src_shift + ry * stride + 3 * rx0
+                found.add(_row_class(at, rx1 - rx0))
+                longest = max(longest, (rx1 - rx0, at % 4))
+            most = max(most, ry1 - ry0)
+    return found, longest, most
+
+
 def odd_pad(pixels):
     """1 or 2: what makes rows of `pixels` 3-byte pixels an odd number of bytes apart, so that 16 rows take every address mod 16 (4: mod 4)."""
     return 2 if pixels % 2 else 1
@@ -95,12 +176,31 @@ COPY_WIDTHS = (1, 2, 5, 11, 16, 21, 43, 48, 63, 64, 65, 129)       # area at rat
 SOURCE_ROWS = 37                                                   # 37 -> 16 rows: no integer ratio
 # area: 'ratio' 2 w + 1 -> w (no integer but at w = 1, which has none) and 37 -> 16, 'copy' w x 16 as it is;  crop_area: the crop 2 w + 1 x 37 that
 # starts on whole pixels on both axes (the staged raw rows are the patch) and on half pixels on both;  dof: the caps 16 and 3
-STORE_SWEEPS = [('area', 'ratio'), ('area', 'copy'), ('crop_area', 'oo'), ('crop_area', 'ee'), ('dof', 16), ('dof', 3)]
+# enlarge: the crop (2 w + 2) // 3 x 11 -> w x 16 that starts on whole pixels on both axes (the pass along the rows reads the staged raw rows)
+# and on half pixels on both (it reads the patch);  sharpen: a radius whose halo is a dword and a half, and the largest
+STORE_SWEEPS = [('area', 'ratio'), ('area', 'copy'), ('crop_area', 'oo'), ('crop_area', 'ee'), ('dof', 16), ('dof', 3),
+                ('enlarge', 'oo'), ('enlarge', 'ee'), ('sharpen', 2), ('sharpen', 24)]
 DOF_FOCUS, DOF_APERTURE = 100.0, 16.0
+# widths of their own that are taller than STORE_ROWS, {width: rows}: three tiles across and three (two) down -- enlarge's second band of tile
+# rows 0 .. 15 and a third that is cut, sharpen's trips over tile rows 16 .. 31 and a second band
+TALL = {'enlarge': {130: 40}, 'sharpen': {130: 40}}
+ENLARGE_CROP_ROWS = {STORE_ROWS: 11, 40: 27}
+SHARPEN_AMOUNT = 512
 
 
 def store_widths(entry, variant):
-    return COPY_WIDTHS if (entry, variant) == ('area', 'copy') else STORE_WIDTHS
+    return COPY_WIDTHS if (entry, variant) == ('area', 'copy') else STORE_WIDTHS + tuple(TALL.get(entry, ()))
+
+
+def store_rows(entry, w):
+    return TALL.get(entry, {}).get(w, STORE_ROWS)
+
+
+def radius_taps(R):
+    """sharpen_cases.taps_of at a sigma whose radius is R: (w_0, .., w_R)."""
+    sigma = (R - 0.1) / 3.0
+    assert sc.radius_of(sigma) == R
+    return sc.taps_of(sigma)
 
 
 def store_stride(w):
@@ -117,7 +217,15 @@ def sweep_depth(W, H):
 @functools.lru_cache(maxsize=None)
 def store_case(entry, variant, w):
     """(the call's arguments after the module: a tuple, its keywords, the twin's bytes [1, 16, w, 3]) of one width of a store sweep."""
-    h, kw = STORE_ROWS, dict(pad=1, out_pad=odd_pad(w))
+    h, kw = store_rows(entry, w), dict(pad=1, out_pad=odd_pad(w))
+    if entry == 'enlarge':
+        crop = ((2 * w + 2) // 3, ENLARGE_CROP_ROWS[h])
+        frames = gc.photo_like(crop[1] + cc.OFF[variant][1], crop[0] + cc.OFF[variant][0], 7 + w)[None]
+        assert (cc.start(frames.shape[2], crop[0])[1], cc.start(frames.shape[1], crop[1])[1]) == {'oo': (False, False), 'ee': (True, True)}[variant]
+        return (frames, crop, (w, h)), kw, ec.twin_enlarge(frames, crop, (w, h))
+    if entry == 'sharpen':
+        frames, taps = gc.photo_like(h, w, 7 + w)[None], radius_taps(variant)
+        return (frames, taps, SHARPEN_AMOUNT), kw, sc.twin_sharpen(frames, taps, SHARPEN_AMOUNT)
     if entry == 'area':
         frames = gc.photo_like(h, w, 7 + w)[None] if variant == 'copy' else gc.photo_like(SOURCE_ROWS, 2 * w + 1, 7 + w)[None]
         return (frames, w, h), kw, ac.twin_reduce(frames, w, h)
@@ -136,18 +244,24 @@ def store_sweep_classes(entry, variant):
     """The (lead, nx) classes a store sweep reaches: from its widths and strides alone, the outputs on their allocations' starts."""
     found = set()
     for w in store_widths(entry, variant):
-        found |= store_classes(w, STORE_ROWS, store_stride(w))
+        found |= store_classes(w, store_rows(entry, w), store_stride(w))
     return found
 
 
 # -- the fetch sweep -----------------------------------------------------------------------------
 SRC_SHIFTS = (0, 1, 2, 3)
-FETCH_SWEEPS = [('area', None), ('crop_area', 'oo'), ('crop_area', 'ee'), ('dof', 16)]
+FETCH_SWEEPS = [('area', None), ('crop_area', 'oo'), ('crop_area', 'ee'), ('dof', 16), ('enlarge', 'oo'), ('enlarge', 'ee'), ('sharpen', 7)]
 # four consecutive widths: every 3 len mod 4.  area, crop_area: a strip of 340 (339) pixels and a shorter one in the first tile, a second tile
-# that starts elsewhere; dof: two tiles, the second one's window starts 48 pixels in
-FETCH_WIDTHS = {'area': (380, 381, 382, 383), 'crop_area': (371, 372, 373, 374), 'dof': (69, 70, 71, 72)}
-FETCH_ROWS = {'area': 9, 'crop_area': 9, 'dof': 7}
+# that starts elsewhere; dof: two tiles, the second one's window starts 48 pixels in; enlarge: the crop's width, two tiles whose spans the
+# patch's borders cut; sharpen: two tiles, the second one's rows start 57 pixels in
+FETCH_WIDTHS = {'area': (380, 381, 382, 383), 'crop_area': (371, 372, 373, 374), 'dof': (69, 70, 71, 72), 'enlarge': (69, 70, 71, 72), 'sharpen': (69, 70, 71, 72)}
+FETCH_ROWS = {'area': 9, 'crop_area': 9, 'dof': 7, 'enlarge': 9, 'sharpen': 7}
 FETCH_TARGET = (70, 5)
+
+
+def enlarge_fetch_target(W, H):
+    """(w, h) of the enlargement of a crop W x H in the fetch sweep: no integer ratio on either axis."""
+    return W + 9, H + 4
 
 
 def fetch_stride(W):
@@ -159,6 +273,13 @@ def fetch_case(entry, variant, W):
     """(arguments, keywords without src_shift, the twin's bytes) of one width of a fetch sweep; W: the width of what is fetched from -- the
     source, the crop, the frame."""
     H, kw = FETCH_ROWS[entry], dict(out_pad=3)
+    if entry == 'enlarge':
+        crop, size = (W, H), enlarge_fetch_target(W, H)
+        frames = gc.photo_like(H + cc.OFF[variant][1], W + cc.OFF[variant][0], 3 + W)[None]
+        return (frames, crop, size), dict(kw, pad=odd_pad(frames.shape[2])), ec.twin_enlarge(frames, crop, size)
+    if entry == 'sharpen':
+        frames, taps = gc.photo_like(H, W, 3 + W)[None], radius_taps(variant)
+        return (frames, taps, SHARPEN_AMOUNT), dict(kw, pad=odd_pad(W)), sc.twin_sharpen(frames, taps, SHARPEN_AMOUNT)
     if entry == 'area':
         frames = gc.photo_like(H, W, 3 + W)[None]
         return (frames,) + FETCH_TARGET, dict(kw, pad=odd_pad(W)), ac.twin_reduce(frames, *FETCH_TARGET)
@@ -181,9 +302,66 @@ def fetch_sweep_classes(entry, variant):
             elif entry == 'crop_area':
                 FW, FH = W + cc.OFF[variant][0], H + cc.OFF[variant][1]
                 found |= crop_area_fetch_classes(FW, FH, (W, H), FETCH_TARGET, fetch_stride(FW), src_shift)
+            elif entry == 'enlarge':
+                FW, FH = W + cc.OFF[variant][0], H + cc.OFF[variant][1]
+                found |= enlarge_fetch_classes(FW, FH, (W, H), enlarge_fetch_target(W, H), fetch_stride(FW), src_shift)[0]
+            elif entry == 'sharpen':
+                found |= sharpen_fetch_classes(W, H, variant, fetch_stride(W), src_shift)
             else:
                 found |= dof_fetch_classes(W, H, variant, fetch_stride(W), src_shift)
     return found
+
+
+# -- sharpen at every radius ---------------------------------------------------------------------
+SHARPEN_RADII = tuple(range(1, MAX_RADIUS + 1))
+# taps that do not fall with the distance and add up to 32768 = 20000 + 2 (1000 + 5000 + 384): a tap taken at another distance shows
+ODD_TAPS = (20000, 1000, 5000, 384)
+
+
+def sharpen_radius_frames(R):
+    """[(W, H)] of the frames of a radius, each with H >= 4 rows an odd number of bytes apart, so that every tile stages rows at every shift:
+      three tiles whose middle one has its whole halo inside the frame, the first one's left halo and the last one's right halo -- all R of
+      it -- beyond it;
+      from R = 2 on, three tiles whose last is m < R wide: the middle one's right halo lies R - m pixels beyond the frame (0 < right < R);
+      one tile narrower than 64: both halos beyond the frame.
+    From R = 5 on the frames have fewer rows than R: every staged row above and below the tile is a border row again."""
+    wide = (2 * TILE_X + R + 1 + R % 3, 5 + R % 4)
+    cut = [(2 * TILE_X + 1 + (R // 2 + 3 * (R % 5)) % (R - 1), 4)] if R >= 2 else []
+    return [wide] + cut + [(1 + 5 * R % 63, 7)]
+
+
+@functools.lru_cache(maxsize=None)
+def sharpen_radius_case(R, frame, taps=None):
+    """(arguments, keywords, the twin's bytes) of one frame of a radius: the source R mod 4 bytes off its allocation."""
+    W, H = frame
+    frames, taps = gc.photo_like(H, W, 11 + R + W)[None], taps or radius_taps(R)
+    assert len(taps) == R + 1
+    kw = dict(pad=odd_pad(W), out_pad=odd_pad(W), src_shift=R % 4)
+    return (frames, taps, SHARPEN_AMOUNT), kw, sc.twin_sharpen(frames, taps, SHARPEN_AMOUNT)
+
+
+def sharpen_radius_classes(R):
+    found = set()
+    for W, H in sharpen_radius_frames(R):
+        found |= sharpen_stage_classes(W, H, R, fetch_stride(W), R % 4)
+    return found
+
+
+# -- enlarge at a full LDS row -------------------------------------------------------------------
+# (frame, crop, size), W x H each.  190 targets from 189 sources: the 64 targets of the middle tile lie at 63 .. 126, 64 positions in a row,
+# so their taps are the 67 patch pixels 62 .. 128; 46 from 45: the middle band's 16 targets lie at 15 .. 30, their taps are the 19 rows
+# 14 .. 32.  The first crop starts on half pixels on both axes: 68 raw pixels and 20 raw rows, which is all an LDS row and the staged
+# rectangle hold; the second on whole pixels: the pass along the rows reads the staged raw rows, 67 pixels of 19 rows.  In both the first
+# and the last tile's and band's span is cut by the clamp at the patch's border.
+FULL_ROWS = [((191, 47), (189, 45), (190, 46)), ((192, 48), (189, 45), (190, 46))]
+
+
+@functools.lru_cache(maxsize=None)
+def full_row_case(i):
+    """(arguments, keywords without src_shift, the twin's bytes) of FULL_ROWS[i]."""
+    (W, H), crop, size = FULL_ROWS[i]
+    frames = gc.photo_like(H, W, 31 + i)[None]
+    return (frames, crop, size), dict(pad=odd_pad(W), out_pad=odd_pad(size[0])), ec.twin_enlarge(frames, crop, size)
 
 
 # -- an exact area reduction without a weight matrix ------------------------------------------------

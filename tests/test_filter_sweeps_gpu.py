@@ -1,16 +1,19 @@
-"""The three byte-frame filters on the GPU (kbe_area_reduce_u8, kbe_crop_area_u8, kbe_dof_u8) where their own test modules do not reach: every
-alignment class of the tile store and of the row fetch -- one definition, csrc/kbe_rows.h, which every tile kernel runs at its own loop shape (so
-the sweeps over these three also hold kbe_enlarge_u8's and kbe_sharpen_u8's store) --; the sides' limit of 65535; and the radius of the blur
-as the device computes it, at its ties, at products that overflow and on subnormal depths.  Byte for byte against the twins, or at the sides'
-limit against references that work there (tests/filter_sweep_cases.py; what they rest on: tests/test_filter_sweeps.py), every buffer from
-guarded.Guard on both poisons."""
+"""The five tile filters on the GPU (kbe_area_reduce_u8, kbe_crop_area_u8, kbe_dof_u8, kbe_enlarge_u8, kbe_sharpen_u8) where their own test
+modules do not reach: every alignment class of the tile store and of the row fetch -- one definition, csrc/kbe_rows.h, which every tile kernel
+runs at its own loop shape, so each of the five is swept on its own --; sharpen's halo staging at every radius 1 .. 24, and enlarge at the
+crops that fill its LDS row and its staged rectangle; of the first three the sides' limit of 65535 (enlarge's and sharpen's: their own
+modules); and the radius of the blur as the device computes it, at its ties, at products that overflow and on subnormal depths.  Byte for byte
+against the twins, or at the sides' limit against references that work there (tests/filter_sweep_cases.py; what they rest on:
+tests/test_filter_sweeps.py), every buffer from guarded.Guard on both poisons."""
 import numpy as np
 import pytest
 import torch
 
 import dof_cases as dc
+import enlarge_gpu as ng
 import filter_gpu as fg
 import filter_sweep_cases as fc
+import sharpen_gpu as sg
 
 pytestmark = pytest.mark.gpu
 
@@ -18,11 +21,12 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope='module')
 def entries():
     """entry -> (its module, its raw call)"""
-    from ken_burns_effect_amd import area, crop_area, dof
+    from ken_burns_effect_amd import area, crop_area, dof, enlarge, sharpen
     assert torch.cuda.is_available(), 'GPU tests need a GPU'
-    for module in (area, crop_area, dof):
+    for module in (area, crop_area, dof, enlarge, sharpen):
         module.load()
-    return {'area': (area, fg.run_area), 'crop_area': (crop_area, fg.run_crop_area), 'dof': (dof, fg.run_dof)}
+    return {'area': (area, fg.run_area), 'crop_area': (crop_area, fg.run_crop_area), 'dof': (dof, fg.run_dof), 'enlarge': (enlarge, ng.run_enlarge),
+            'sharpen': (sharpen, sg.run_sharpen)}
 
 
 def assert_bytes(entries, entry, args, want, poison, **kw):
@@ -41,10 +45,11 @@ def assert_bytes(entries, entry, args, want, poison, **kw):
 @pytest.mark.parametrize('entry, variant', fc.STORE_SWEEPS, ids=str)
 def test_every_lead_at_every_tile_width(entries, entry, variant, poison):
     """16 output rows an odd number of bytes apart -- every address mod 16 -- at every width 1 .. 64 of a single tile, and with a second and a
-    third tile behind it: all 1024 classes of the store (tests/test_filter_sweeps.py), one call per width."""
+    third tile behind it: all 1024 classes of the store (tests/test_filter_sweeps.py), one call per width.  enlarge and sharpen have one
+    width more that is 40 rows: tile rows beyond the first 16 and a second band."""
     for w in fc.store_widths(entry, variant):
         args, kw, want = fc.store_case(entry, variant, w)
-        assert want.shape == (1, fc.STORE_ROWS, w, 3) and 3 * w + kw['out_pad'] == fc.store_stride(w)
+        assert want.shape == (1, fc.store_rows(entry, w), w, 3) and 3 * w + kw['out_pad'] == fc.store_stride(w)
         assert_bytes(entries, entry, args, want, poison, **kw)
 
 
@@ -57,6 +62,31 @@ def test_every_shift_at_every_length(entries, entry, variant, poison):
         args, kw, want = fc.fetch_case(entry, variant, W)
         for src_shift in fc.SRC_SHIFTS:
             assert_bytes(entries, entry, args, want, poison, src_shift=src_shift, **kw)
+
+
+# -- 1b. the code around the fetch that only sharpen and only enlarge have ---------------------------------
+@pytest.mark.parametrize('R', fc.SHARPEN_RADII)
+def test_sharpen_at_every_radius(entries, R):
+    """Every R in 1 .. 24 -- each lays out the kernel's LDS its own way -- on frames where a staged row lies at every shift behind a left halo
+    beyond the frame (3 R bytes rounded up to a dword), in front of a right halo that lies beyond it by all R pixels and by fewer, between
+    both, and with neither; from R = 8 on with fewer rows than R (tests/test_filter_sweeps.py).  At R = 3 also with taps that do not fall
+    with the distance."""
+    for frame in fc.sharpen_radius_frames(R):
+        for taps in (None, fc.ODD_TAPS) if R == len(fc.ODD_TAPS) - 1 else (None,):
+            args, kw, want = fc.sharpen_radius_case(R, frame, taps)
+            for poison in fg.POISONS:
+                assert_bytes(entries, 'sharpen', args, want, poison, **kw)
+
+
+@pytest.mark.parametrize('poison', fg.POISONS, ids=hex)
+@pytest.mark.parametrize('i', range(len(fc.FULL_ROWS)), ids=['half', 'whole'])
+def test_enlarge_at_a_full_raw_row(entries, i, poison):
+    """190 x 46 from a crop 189 x 45: the middle tile stages 68 raw pixels at a shift of 3 -- all 52 dwords of an LDS row -- in 20 rows where
+    the crop starts on half pixels, and 67 pixels of 19 rows, read by the pass along the rows itself, where it starts on whole pixels; the
+    first and the last tile's span is cut by the clamp at the patch's border (tests/test_filter_sweeps.py).  The source 0 .. 3 bytes off."""
+    args, kw, want = fc.full_row_case(i)
+    for src_shift in fc.SRC_SHIFTS:
+        assert_bytes(entries, 'enlarge', args, want, poison, src_shift=src_shift, **kw)
 
 
 # -- 2. the sides' limit -------------------------------------------------------------------------------
