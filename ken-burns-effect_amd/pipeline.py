@@ -11,6 +11,7 @@ weights of ``Semantics`` come from a file (``semantics_path``) instead of a torc
 video through an ``ffmpeg`` binary if one is on PATH (OpenCV / moviepy are not dependencies) --
 otherwise the ``.mp4`` holds Motion-JPEG (ISO base media file written here, no external encoder).  Returns the frame list.
 """
+import collections
 import math
 import os
 import shutil
@@ -174,152 +175,50 @@ class Pipeline():
             return self._run(tensorImage, zoom_settings, output_path, inpaint_depth, pretrained_estim)
 
     @torch.no_grad()
-    def render(self, tensorImage, zoom_settings):
-        """The clip's frames as a uint8 [steps,H,W,3] tensor in HBM, and nothing written: what _run renders, with the instance's width, lens,
-        shutter, grade, sharpening and layers, up to process_kenburns(keep_on_device=True).  For callers that go on with the frames on the device (slideshow.py).  _run is kept
-        byte for byte what it was, so its first half is repeated here: an option that _run learns has to be taught to this method as well
-        (tests/test_transition_gpu.py holds the two to the same process_kenburns call)."""
-        from .utils import miopen_tuned_once
+    def render(self, tensorImage, zoom_settings, bgr=True, layers=True):
+        """The clip's frames as a uint8 [steps,H,W,3] tensor in HBM, and nothing written: the frames of _run -- the same plan (plan_clip) and
+        the same render (_frames), with the instance's width, lens, shutter, grade, sharpening and layers.  bgr: the image's channel order, B,
+        G, R unless the caller fed R, G, B; layers=False: without the instance's caption and watermark.  For callers that go on with the
+        frames on the device (slideshow.py)."""
         with common.on_device_of(getattr(self, 'device', torch.device('cpu'))):
-            auto = getattr(self, 'miopen_find', False) == 'auto'
-            wide = out_width(getattr(self, 'width', None))
-            enlarging = {'enlarge': True} if enlarge_switch(getattr(self, 'enlarge', None)) else {}
-            out_size = None
-            if wide is not None:
-                try:
-                    out_size = width_size(wide, tensorImage.size(3), tensorImage.size(2), zoom_settings, **enlarging)
-                except ValueError as e:
-                    raise ValueError('width %d: %s' % (wide, e)) from None
-            elif enlarging:
-                raise ValueError('enlarge (KBE_ENLARGE, --enlarge): only with a width')
-            grow = {'enlarge': True} if out_size is not None and grows(out_size, zoom_settings) else {}
-            lens_at = lens_request(getattr(self, 'aperture', None), getattr(self, 'focus', None), getattr(self, 'focus_to', None))
-            if lens_at is not None:
-                lens_at = lens_points(lens_at, tensorImage.size(3), tensorImage.size(2), zoom_settings)
-            open_for = shutter_request(getattr(self, 'shutter', None), getattr(self, 'shutter_samples', None))
-            # (the layers' colour bytes in the frames' order: B, G, R, unless the caller fed R, G, B and says so in self.overlay_bgr)
-            layers = layers_of(self, out_size or (lambda: (tensorImage.size(3), tensorImage.size(2))), bgr=getattr(self, 'overlay_bgr', True))
-            graded = grade_of(self, bgr=getattr(self, 'overlay_bgr', True))
-            crisp = sharpen_of(self)
-            with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
-                self.estimate(tensorImage)
-                lens = {}
-                if lens_at is not None:
-                    from . import dof
-                    aperture, near, far = lens_at
-                    lens = {'lens': dof.Lens(dof.focus_depth(self.objectCommon['tensorRawDepth'], *near), dof.focus_depth(self.objectCommon['tensorRawDepth'], *far), aperture)}
-                return with_layers(layers, with_sharpen(crisp, with_grade(graded, common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
-                                                'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
-                                                'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=True,
-                                               **({} if out_size is None else {'out_size': out_size}), **grow, **lens,
-                                               **({} if open_for is None else {'shutter': open_for})))))
+            plan = plan_clip(self, tensorImage, zoom_settings, bgr, writing=False, layers=layers)
+            return plan.filtered(self._frames(tensorImage, zoom_settings, plan, keep_on_device=True))
 
     def tuning_tag(self, width, height):
         """What MIOpen is tuned for, once per machine (utils.miopen_tuned_once): this pipeline's networks at this image size."""
         return '%dx%d-%s%s%s' % (width, height, 'partial' if self.partial_inpainting else 'plain', '-dolly' if self.dolly else '',
                                  '-pretrain' if isinstance(self.moduleRefine, RefinePretrained) else '')
 
-    def _run(self, tensorImage, zoom_settings, output_path, inpaint_depth, pretrained_estim):
+    def _frames(self, tensorImage, zoom_settings, plan, keep_on_device, inpaint_depth=False):
+        """The one render: the networks (estimate), then the frame loop with the plan's keywords -- each absent unless set, so without a width,
+        a lens or a shutter the call is what it always was.  A uint8 [steps,H,W,3] tensor in HBM, or with keep_on_device=False a list of host frames."""
         from .utils import miopen_tuned_once
         auto = getattr(self, 'miopen_find', False) == 'auto'
-        # KBE_GIF=1 (Pipeline(gif=True), kbe.py --gif): the frames stay in HBM as well and 3d_kbe.gif is encoded from them (gif.py); every
-        # other file is then written as it would have been without the switch, by the same route's encoder.  Its width and rate (gif_shape)
-        # are looked at before any network runs: the frames are the image's size, and a GIF wider than them is refused
-        gif_on = output_path is not None and gif_switch(getattr(self, 'gif', None))
-        if gif_on:
-            gif_wide, gif_every = gif_shape(getattr(self, 'gif_width', None), getattr(self, 'gif_fps', None))
-            if gif_wide is not None and gif_wide > tensorImage.size(3) and not enlarge_switch(getattr(self, 'enlarge', None)):      # (enlarged frames may be wider: see below)
-                raise ValueError('a GIF %d pixels wide from an image %d wide: the GIF is only ever reduced' % (gif_wide, tensorImage.size(3)))
-        # KBE_Y4M=1 (Pipeline(y4m=True), kbe.py --y4m): the frames stay in HBM as with the GIF, and 3d_kbe.y4m is converted from them (yuv.py)
-        y4m_on = output_path is not None and y4m_switch(getattr(self, 'y4m', None))
-        # KBE_WIDTH (Pipeline(width=), kbe.py --width): looked at before any network runs as well
-        wide = out_width(getattr(self, 'width', None))
-        # KBE_ENLARGE=1 (Pipeline(enlarge=True), kbe.py --enlarge): a width above the crop's is then taken, and the crop enlarged (enlarge.py)
-        enlarging = {'enlarge': True} if enlarge_switch(getattr(self, 'enlarge', None)) else {}
-        out_size = None
-        if wide is not None:
-            try:
-                out_size = width_size(wide, tensorImage.size(3), tensorImage.size(2), zoom_settings, **enlarging)
-            except ValueError as e:
-                raise ValueError('width %d: %s' % (wide, e)) from None
-            if gif_on and gif_wide is not None and gif_wide > out_size[0]:
-                raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif_wide, out_size[0]))
-        elif enlarging:
-            raise ValueError('enlarge (KBE_ENLARGE, --enlarge): only with a width')
-        grow = {'enlarge': True} if out_size is not None and grows(out_size, zoom_settings) else {}
-        # KBE_APERTURE, KBE_FOCUS, KBE_FOCUS_TO (Pipeline(aperture=, focus=, focus_to=), kbe.py --aperture --focus --focus-to): looked at
-        # before any network runs as well; the focus DEPTHS are read from the estimated depth below
-        lens_at = lens_request(getattr(self, 'aperture', None), getattr(self, 'focus', None), getattr(self, 'focus_to', None))
-        if lens_at is not None:
-            lens_at = lens_points(lens_at, tensorImage.size(3), tensorImage.size(2), zoom_settings)
-        # KBE_SHUTTER, KBE_SHUTTER_SAMPLES (Pipeline(shutter=, shutter_samples=), kbe.py --shutter --shutter-samples): before any network runs too
-        open_for = shutter_request(getattr(self, 'shutter', None), getattr(self, 'shutter_samples', None))
-        # KBE_OVERLAY, KBE_CAPTION and their kin (Pipeline(overlay=, caption=, ...), kbe.py --overlay --caption): the file is read and the caption
-        # drawn before any network runs too, for frames of the size they will have; the frames then stay in HBM, where the layers are composited
-        layers = layers_of(self, out_size or (lambda: (tensorImage.size(3), tensorImage.size(2))), bgr=not pretrained_estim)
-        # KBE_LUT, KBE_GRADE, KBE_LOOK, KBE_LUT_STRENGTH (Pipeline(lut=, grade=, look=, lut_strength=), kbe.py --lut --grade --look): the file is
-        # read and the table baked before any network runs too; the frames then stay in HBM, where they are graded before the layers go on
-        graded = grade_of(self, bgr=not pretrained_estim)
-        # KBE_SHARPEN (Pipeline(sharpen=), kbe.py --sharpen): read and checked before any network runs too; the frames then stay in HBM, where
-        # they are sharpened after the grade and before the layers go on
-        crisp = sharpen_of(self)
         with miopen_tuned_once(self.tuning_tag(tensorImage.size(3), tensorImage.size(2)) if auto else '', getattr(self, 'device', 'cpu'), enabled=auto):
             self.estimate(tensorImage)
             if inpaint_depth:
                 raise NotImplementedError('two-network depth inpainting is broken in the reference (common.py:50-69)')
-            # KBE_JPEG=device, a Motion-JPEG video (no ffmpeg binary) and no PNG frames: the frames stay in HBM, the GPU encodes them and the
-            # streams come to the host, a tenth of the pixels' bytes.  KBE_PNG=device and PNG frames asked for: the frames stay in HBM as
-            # well and the GPU encodes the PNG files (png_encoder); the video then comes from the same frames in HBM if the first
-            # condition holds but for the PNG frames, and from the frames fetched raw otherwise.  Any other combination takes the host
-            # route below
-            jpeg_on_device = output_path is not None and shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
-            png_on_device = output_path is not None and bool(self.output_frames) and png_encoder() == 'device'
-            video_from_hbm = jpeg_on_device and (png_on_device or not self.output_frames)
-            on_device = png_on_device or video_from_hbm or gif_on or y4m_on or bool(layers) or graded is not None or crisp is not None
-            lens = {}
-            if lens_at is not None:
-                from . import dof
-                aperture, near, far = lens_at
-                lens = {'lens': dof.Lens(dof.focus_depth(self.objectCommon['tensorRawDepth'], *near), dof.focus_depth(self.objectCommon['tensorRawDepth'], *far), aperture)}
-            frames = common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
-                                              'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
-                                              'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=on_device,
-                                             **({} if out_size is None else {'out_size': out_size}), **grow, **lens,
-                                             **({} if open_for is None else {'shutter': open_for}))     # (without a width, a lens or a shutter the call is what it was)
-        if on_device:
-            with_grade(graded, frames)                                                  # the grade: in place, before the layers, which are never graded
-            with_sharpen(crisp, frames)                                                 # the sharpening: in place, the last thing done to the picture itself
-            with_layers(layers, frames)                                                 # the caption, then the watermark: in place, before every output
-            if output_path is None:                                                     # (only with a grade, a sharpening or a layer: nothing is written)
-                host = frames.cpu().numpy()
-                return [host[i] for i in range(host.shape[0])]
-            os.makedirs(output_path, exist_ok=True)
-            # (the frames are in the INPUT's channel order, as below: the encoders read B, G, R unless --pretrained-estim)
-            if png_on_device:
-                from . import _native
-                write_frames(os.path.join(output_path, 'frames'), None, pngs=_native.kernels().png_encode(frames, bgr=not pretrained_estim))
-            if gif_on:
-                from . import area, gif
-                gif_size = None if gif_wide is None else area.size_for(frames.shape[2], frames.shape[1], width=gif_wide)
-                gif.write_gif(os.path.join(output_path, '3d_kbe.gif'), frames, fps=25, bgr=not pretrained_estim, dither=gif_dither(getattr(self, 'gif_dither', None)),
-                              size=gif_size, every=gif_every)
-            if y4m_on:
-                from . import yuv
-                yuv.write_y4m(os.path.join(output_path, '3d_kbe.y4m'), frames, fps=25, bgr=not pretrained_estim)
-            if video_from_hbm:
-                encoded = jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=not pretrained_estim)
-                # forth and back (:131): every distinct frame was encoded once, the way back is the same byte objects again
-                write_video(os.path.join(output_path, '3d_kbe.mp4'), None, fps=25, jpegs=encoded + encoded[-2::-1], frame_size=tuple(frames.shape[1:3]))
-            host = frames.cpu().numpy()                                                 # the return value (with video_from_hbm: fetched after the video is written)
-            out = [host[i] for i in range(host.shape[0])]
-            png_on_host = bool(self.output_frames) and not png_on_device               # (only with the GIF or the y4m file: the PNG frames from the fetched frames, as without it)
-            if png_on_host or not video_from_hbm:
-                rgb = out if pretrained_estim else [f[:, :, ::-1] for f in out]
-                if png_on_host:
-                    write_frames(os.path.join(output_path, 'frames'), rgb)
-                if not video_from_hbm:
-                    write_video(os.path.join(output_path, '3d_kbe.mp4'), rgb + rgb[-2::-1], fps=25)
-            return out
+            return common.process_kenburns({'dblSteps': np.linspace(0.0, 1.0, self.steps).tolist(),
+                                            'objectFrom': zoom_settings['objectFrom'], 'objectTo': zoom_settings['objectTo'],
+                                            'boolInpaint': True, 'dolly': self.dolly}, self.objectCommon, self.moduleInpaint, keep_on_device=keep_on_device,
+                                           **plan.keywords(self.objectCommon))
+
+    def _run(self, tensorImage, zoom_settings, output_path, inpaint_depth, pretrained_estim):
+        bgr = not pretrained_estim          # (the frames are in the INPUT's channel order: B, G, R from cv2.imread unless --pretrained-estim)
+        plan = plan_clip(self, tensorImage, zoom_settings, bgr, writing=output_path is not None)
+        # KBE_JPEG=device, a Motion-JPEG video (no ffmpeg binary) and no PNG frames: the frames stay in HBM, the GPU encodes them and the
+        # streams come to the host, a tenth of the pixels' bytes.  KBE_PNG=device and PNG frames asked for: the frames stay in HBM as
+        # well and the GPU encodes the PNG files (png_encoder); the video then comes from the same frames in HBM if the first
+        # condition holds but for the PNG frames, and from the frames fetched raw otherwise.  The GIF, the y4m file, a grade, a
+        # sharpening and a layer keep the frames in HBM too.  Any other combination takes the host route below
+        jpeg_on_device = output_path is not None and mjpeg_from_hbm()
+        png = output_path is not None and bool(self.output_frames)
+        png_on_device = png and png_encoder() == 'device'
+        video_from_hbm = jpeg_on_device and (png_on_device or not png)
+        on_device = png_on_device or video_from_hbm or plan.gif is not None or plan.y4m or bool(plan.layers) or plan.grade is not None or plan.sharpen is not None
+        frames = self._frames(tensorImage, zoom_settings, plan, on_device, inpaint_depth)
+        if on_device:                       # (output_path None: only with a grade, a sharpening or a layer, and nothing is written)
+            return write_outputs(plan.filtered(frames), output_path, '3d_kbe', bgr, True, png, plan.gif, getattr(self, 'gif_dither', None), plan.y4m, video_from_hbm)
         if output_path is not None:
             os.makedirs(output_path, exist_ok=True)
             # channel order on disk as the reference produces it: frames are in the INPUT's channel order
@@ -453,8 +352,6 @@ def layers_of(pipe, size, bgr=True):
     are applied -- the caption, then the watermark -- (overlay.layers_for): what it was told, else the environment's twins; [] without
     either.  ValueError whose text begins with the option at fault."""
     from . import overlay
-    if getattr(pipe, 'no_layers', False):                           # (slideshow.make: the layers are the show's, not a clip's)
-        return []
     request = overlay.layers_request(*[getattr(pipe, name, None) for name in overlay.OPTIONS])
     if request is None:
         return []
@@ -631,6 +528,107 @@ def lens_points(request, W, H, zoom_settings):
         if not (0.0 <= u <= W - 1 and 0.0 <= v <= H - 1):
             raise ValueError('%s %g,%g: the image is %dx%d: a pixel of the photo, 0..%d and 0..%d' % (what, u, v, W, H, W - 1, H - 1))
     return aperture, focus, focus_to
+
+
+class ClipPlan(collections.namedtuple('ClipPlan', 'out_size grow lens_at shutter layers grade sharpen gif y4m')):
+    """What plan_clip decides about a clip on the host, before any network runs.  out_size: (w, h) of every output, or None for the image's;
+    grow: the crop is enlarged to it, not reduced; lens_at: lens_points' answer or None; shutter: a shutter.Shutter or None; layers: the caption
+    and the watermark, fitted to the frames ([] without either); grade, sharpen: grade_of's and sharpen_of's answers or None; gif: (its width
+    or None for the frames' own, every how many frames it keeps), or None where no GIF is written; y4m: whether the y4m file is."""
+    __slots__ = ()
+
+    def keywords(self, estimated):
+        """process_kenburns' keywords: out_size, enlarge, lens and shutter, each absent unless set.  estimated: Pipeline.estimate's
+        objectCommon -- the lens reads its focus depths from the estimated depth, and nothing else looks at it."""
+        keywords = {} if self.out_size is None else {'out_size': self.out_size}
+        if self.grow:
+            keywords['enlarge'] = True
+        if self.lens_at is not None:
+            from . import dof
+            aperture, near, far = self.lens_at
+            keywords['lens'] = dof.Lens(dof.focus_depth(estimated['tensorRawDepth'], *near), dof.focus_depth(estimated['tensorRawDepth'], *far), aperture)
+        if self.shutter is not None:
+            keywords['shutter'] = self.shutter
+        return keywords
+
+    def filtered(self, frames):
+        """The frames, a uint8 [n,H,W,3] tensor in HBM, in place: graded, then sharpened -- the last thing done to the picture itself --, then
+        under the caption and the watermark, which are neither graded nor sharpened.  Before every output."""
+        return with_layers(self.layers, with_sharpen(self.sharpen, with_grade(self.grade, frames)))
+
+
+def plan_clip(pipe, image, zoom_settings, bgr, writing, layers=True):
+    """The ClipPlan of a Pipeline for an image [1,3,H,W] -- of which only the size is read, and only for an option that needs it -- under these
+    windows: every option read (what the instance was told, else the environment's twin: the readers above), checked and made ready -- the
+    layers' files read and drawn, the grade's table baked -- on the host, before any network runs.  bgr: the frames' channel order, for the layers and the grade; writing: files are written, so the GIF and the y4m file are
+    looked at; layers=False: without the instance's caption and watermark.  ValueError for the first fault found, in this order."""
+    def told(name):
+        return getattr(pipe, name, None)
+
+    def size():
+        return int(image.size(3)), int(image.size(2))
+    enlarging = enlarge_switch(told('enlarge'))                     # (a width above the crop's is then taken, and the crop enlarged: enlarge.py)
+    gif = gif_shape(told('gif_width'), told('gif_fps')) if writing and gif_switch(told('gif')) else None
+    if gif is not None and gif[0] is not None and gif[0] > size()[0] and not enlarging:      # (enlarged frames may be wider: see below)
+        raise ValueError('a GIF %d pixels wide from an image %d wide: the GIF is only ever reduced' % (gif[0], size()[0]))
+    wide, out_size = out_width(told('width')), None
+    if wide is not None:
+        try:
+            out_size = width_size(wide, *size(), zoom_settings, **({'enlarge': True} if enlarging else {}))
+        except ValueError as e:
+            raise ValueError('width %d: %s' % (wide, e)) from None
+        if gif is not None and gif[0] is not None and gif[0] > out_size[0]:
+            raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif[0], out_size[0]))
+    elif enlarging:
+        raise ValueError('enlarge (KBE_ENLARGE, --enlarge): only with a width')
+    # (the lens's focus POINTS: its focus depths are read from the estimated depth, in ClipPlan.keywords)
+    lens_at = lens_request(told('aperture'), told('focus'), told('focus_to'))
+    if lens_at is not None:
+        lens_at = lens_points(lens_at, *size(), zoom_settings)
+    shutter = shutter_request(told('shutter'), told('shutter_samples'))
+    return ClipPlan(out_size, out_size is not None and grows(out_size, zoom_settings), lens_at, shutter,
+                    layers_of(pipe, out_size or size, bgr) if layers else [], grade_of(pipe, bgr), sharpen_of(pipe),
+                    gif, writing and y4m_switch(told('y4m')))
+
+
+def mjpeg_from_hbm():
+    """Whether the video is Motion-JPEG encoded on the GPU from frames that lie in HBM: no ffmpeg binary, and KBE_JPEG=device."""
+    return shutil.which('ffmpeg') is None and jpeg_encoder()[0] == 'device'
+
+
+def write_outputs(frames, out_dir, stem, bgr, back, png, gif, dither, y4m, video_from_hbm):
+    """Every output of frames that lie in HBM, a uint8 [n,H,W,3] tensor in the channel order bgr, as out_dir/stem.mp4 and, where asked for,
+    frames/*.png (png), stem.gif (gif: ClipPlan's (width, every); dither: gif_dither's argument) and stem.y4m (y4m) -> the frames as a list
+    of host arrays, fetched once.  The device goes first -- the PNG files under KBE_PNG=device, the GIF, the y4m file, the video where
+    video_from_hbm (mjpeg_from_hbm, or less: the caller's decision) --, then the fetch, then the host writes what the device did not.
+    back: the clip plays forth and back in every stream (pipeline.py:131).  out_dir None: nothing is written."""
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        to_and_fro = {} if back else {'back': False}
+        png_on_device = png and png_encoder() == 'device'
+        if png_on_device:
+            from . import _native
+            write_frames(os.path.join(out_dir, 'frames'), None, pngs=_native.kernels().png_encode(frames, bgr=bgr))
+        if gif is not None:
+            from . import area, gif as gif_of
+            size = None if gif[0] is None else area.size_for(frames.shape[2], frames.shape[1], width=gif[0])
+            gif_of.write_gif(os.path.join(out_dir, stem + '.gif'), frames, fps=25, bgr=bgr, dither=gif_dither(dither), size=size, every=gif[1], **to_and_fro)
+        if y4m:
+            from . import yuv
+            yuv.write_y4m(os.path.join(out_dir, stem + '.y4m'), frames, fps=25, bgr=bgr, **to_and_fro)
+        if video_from_hbm:
+            # (every distinct frame is encoded once: the way back is the same byte objects again)
+            encoded = jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=bgr)
+            write_video(os.path.join(out_dir, stem + '.mp4'), None, fps=25, jpegs=encoded + encoded[-2::-1] if back else encoded, frame_size=tuple(frames.shape[1:3]))
+    host = frames.cpu().numpy()                                     # the one fetch (with video_from_hbm: after the video is written)
+    out = [host[i] for i in range(host.shape[0])]
+    if out_dir is not None and (png and not png_on_device or not video_from_hbm):
+        rgb = [f[:, :, ::-1] for f in out] if bgr else out
+        if png and not png_on_device:
+            write_frames(os.path.join(out_dir, 'frames'), rgb)
+        if not video_from_hbm:
+            write_video(os.path.join(out_dir, stem + '.mp4'), rgb + rgb[-2::-1] if back else rgb, fps=25)
+    return out
 
 
 def write_frames(frames_dir, frames_rgb, pngs=None):

@@ -34,7 +34,6 @@ size: the image's, or --width's.
 """
 import getopt
 import os
-import shutil
 import sys
 
 import torch
@@ -197,18 +196,12 @@ def make(images, out_dir, pipe, transition_kind='dissolve', transition_frames=12
     titles, watermark = show_layers(show, layers, bgr)
     P.grade_of(pipe, bgr)                                           # (the clips' grade, which pipe.render applies: refused here, before a network runs)
     P.sharpen_of(pipe)                                              # (... and their sharpening, which pipe.render applies after the grade)
-    gif_on = out_dir is not None and bool(gif)
-    if gif_on:
-        gif_wide, gif_every = P.gif_shape(getattr(pipe, 'gif_width', None), getattr(pipe, 'gif_fps', None))
-        if gif_wide is not None and gif_wide > show['size'][0]:
-            raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif_wide, show['size'][0]))
+    gif = P.gif_shape(getattr(pipe, 'gif_width', None), getattr(pipe, 'gif_fps', None)) if out_dir is not None and gif else None
+    if gif is not None and gif[0] is not None and gif[0] > show['size'][0]:
+        raise ValueError('a GIF %d pixels wide from frames %d wide: the GIF is only ever reduced' % (gif[0], show['size'][0]))
     R, G, B = show['colour']
-    held, pipe.no_layers = getattr(pipe, 'no_layers', False), True  # (the layers are the show's: a clip is rendered without the Pipeline's own)
-    order, pipe.overlay_bgr = getattr(pipe, 'overlay_bgr', True), bgr  # (... and graded, if the Pipeline has a grade, in the frames' channel order)
-    try:
-        clips = [pipe.render(image, zoom) for image, zoom in zip(images, show['zooms'])]
-    finally:
-        pipe.no_layers, pipe.overlay_bgr = held, order
+    # (the layers are the show's: a clip is rendered without the Pipeline's own -- and graded, if the Pipeline has a grade, in the frames' channel order)
+    clips = [pipe.render(image, zoom, bgr=bgr, layers=False) for image, zoom in zip(images, show['zooms'])]
     with P.common.on_device_of(pipe.device):
         for clip, title in zip(clips, titles):
             if title is not None:
@@ -217,34 +210,9 @@ def make(images, out_dir, pipe, transition_kind='dissolve', transition_frames=12
         del clips
         if watermark is not None:
             P.with_layers([watermark], frames)
-        if out_dir is None:
-            host = frames.cpu().numpy()
-            return [host[i] for i in range(host.shape[0])]
-        os.makedirs(out_dir, exist_ok=True)
-        png_on = bool(pipe.output_frames)
-        if png_on and P.png_encoder() == 'device':
-            from . import _native
-            P.write_frames(os.path.join(out_dir, 'frames'), None, pngs=_native.kernels().png_encode(frames, bgr=bgr))
-            png_on = False
-        if gif_on:
-            from . import area, gif as G_
-            size = None if gif_wide is None else area.size_for(frames.shape[2], frames.shape[1], width=gif_wide)
-            G_.write_gif(os.path.join(out_dir, 'slideshow.gif'), frames, fps=25, bgr=bgr, dither=P.gif_dither(getattr(pipe, 'gif_dither', None)), size=size, every=gif_every, back=False)
-        if y4m:
-            from . import yuv
-            yuv.write_y4m(os.path.join(out_dir, 'slideshow.y4m'), frames, fps=25, bgr=bgr, back=False)
-        video_from_hbm = shutil.which('ffmpeg') is None and P.jpeg_encoder()[0] == 'device'
-        if video_from_hbm:
-            P.write_video(os.path.join(out_dir, 'slideshow.mp4'), None, fps=25, jpegs=P.jpeg_encoder()[1].mjpeg_encode(frames, 92, bgr=bgr), frame_size=tuple(frames.shape[1:3]))
-        host = frames.cpu().numpy()                                 # fetched once
-    out = [host[i] for i in range(host.shape[0])]
-    if png_on or not video_from_hbm:
-        rgb = [f[:, :, ::-1] for f in out] if bgr else out
-        if png_on:
-            P.write_frames(os.path.join(out_dir, 'frames'), rgb)
-        if not video_from_hbm:
-            P.write_video(os.path.join(out_dir, 'slideshow.mp4'), rgb, fps=25)
-    return out
+        # (the show plays forth only; its video comes from HBM wherever the GPU encodes it, beside PNG frames written on the host as well)
+        return P.write_outputs(frames, out_dir, 'slideshow', bgr, False, out_dir is not None and bool(pipe.output_frames), gif, getattr(pipe, 'gif_dither', None),
+                               bool(y4m), out_dir is not None and P.mjpeg_from_hbm())
 
 
 def main(argv=None):

@@ -375,9 +375,11 @@ def test_the_layers_of_a_pipeline_and_of_a_slideshow(OV, tmp_path, monkeypatch):
     assert np.array_equal(clips[0], plain) and len(once.rendered) == 2
     request = OV.layers_request(overlay=str(tmp_path / 'logo.png'), overlay_at='top-right', overlay_opacity=0.75, caption='x', caption_size=8, overlay_margin=2)
     pipe.caption = 'not the show\'s'                                         # (the slideshow renders its clips without the Pipeline's own layers)
+    held = dict(vars(pipe))
     show = slideshow.make(images, str(tmp_path / 'show'), pipe, 'dissolve', 2, captions=['First', 'Second\nphoto'], caption_fade=1, layers=request, gif=True, y4m=True)
+    assert dict(vars(pipe)) == held                                          # (... and leaves the Pipeline as it found it: no attribute set, none changed)
     pipe.caption = None
-    assert len(once.rendered) == 2 and once.calls[-2:] == [once.calls[0], once.calls[-3]] and getattr(pipe, 'no_layers') is False
+    assert len(once.rendered) == 2 and once.calls[-2:] == [once.calls[0], once.calls[-3]]
     titled = []
     for clip, words, window in zip(clips, ('First', 'Second\nphoto'), ((0, 4), (2, 6))):
         title = OV.caption_image(words, 8)

@@ -364,4 +364,5 @@ def test_write_gif_takes_back_and_render_exists():
     from ken_burns_effect_amd import gif, pipeline, yuv
     assert inspect.signature(gif.write_gif).parameters['back'].default is True and inspect.signature(gif.write_gif).parameters['back'].kind is inspect.Parameter.KEYWORD_ONLY
     assert inspect.signature(yuv.write_y4m).parameters['back'].default is True
-    assert list(inspect.signature(pipeline.Pipeline.render).parameters) == ['self', 'tensorImage', 'zoom_settings']
+    render = inspect.signature(pipeline.Pipeline.render).parameters
+    assert list(render) == ['self', 'tensorImage', 'zoom_settings', 'bgr', 'layers'] and render['bgr'].default is True and render['layers'].default is True
